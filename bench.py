@@ -10,13 +10,17 @@ branch, 20 in the orientation branch), batch 64 per GPU, fp32, ground 3x320x640 
 and seeded random-init weights (no network).  Inference shards by sample: N>1 runs N replicas with NO data-path
 collective ("weak" scaling); the only collectives are the timing barrier and the max-over-ranks of the elapsed time.
 
+A plain run sets up, warms up, times the `--steps` steps, writes the outputs of the last timed step if `--dump-outputs DIR` is
+given, and prints the line.  `--full` adds everything else the benchmark measures: the CPU baseline and the side legs below.
+
 One JSON line on rank 0 with, besides the contract fields:
   roofline     — for the dominant kernel (largest share of the step among the HIP-event-bracketed dense launches):
                  achieved = algorithmic FLOPs (fp32: MFMA-bound) or bytes (bf16: HBM-bound) of its launches in the timed
                  region / their HIP-event durations; peak from MI355X_MICROARCH.md; traffic = PMC HBM bytes per launch from
                  the committed profiles/ pass (`traffic_source` names it), else null; `whole_step` prices the entire step.
-  cpu_baseline — the CPU oracle (oracle/ccvpe_oracle.py, kind "port") on the host cores, bounded sample, rank 0 / N=1.
-  config       — besides the workload description, the side measurements the default command also runs, as FLAT scalar keys
+  cpu_baseline — `--full`: the CPU oracle (oracle/ccvpe_oracle.py, kind "port") on the host cores, bounded sample, rank 0 / N=1;
+                 null in a plain run.
+  config       — besides the workload description, the side measurements `--full` also runs, as FLAT scalar keys
                  (the driver's record keeps the scalars of `config`; nested objects are dropped): `<leg>_ms`,
                  `<leg>_pairs_per_s`, `<leg>_frac` (whole step against its governing roof), `<leg>_kernel[_frac]`, ... for
                  leg = fwd_bwd_vigor_b64 (BASELINE metric's "(fwd+bwd) VIGOR bs=64": the full training step, with
@@ -80,6 +84,11 @@ def parse():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=64, help="image pairs per GPU per step")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: the CPU baseline(s) and the side legs (--legs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last step as DIR/<name>.npy (float32; a fixed, seeded "
+                         "subset of the batch, at most 64 MB in all)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--graph", action="store_true", help="replay the forward from a captured hipGraph")
     ap.add_argument("--precision", choices=["fp32", "bf16"], default="fp32",
@@ -87,9 +96,9 @@ def parse():
     ap.add_argument("--model", choices=["prior0", "vigor20", "prior180_fov180", "kitti", "oxford"], default="prior0",
                     help="prior0 = C1 (default); vigor20 = C2 (N_rot=20); prior180_fov180 = C4; kitti = C3 forward")
     ap.add_argument("--per-layer", action="store_true", help="print a per-launch-shape table to stderr")
-    ap.add_argument("--no-extra", action="store_true", help="skip the side measurements (config.<leg> summaries)")
+    ap.add_argument("--no-extra", action="store_true", help="--full: skip the side measurements (config.<leg> summaries)")
     ap.add_argument("--legs", default="c2,c1bf16,c4,train,dp",
-                    help="side measurements of the default command: c2, c1bf16, c4, train (fwd+bwd VIGOR), dp (data-parallel "
+                    help="side measurements of --full: c2, c1bf16, c4, train (fwd+bwd VIGOR), dp (data-parallel "
                          "KITTI step; runs only under a process group)")
     ap.add_argument("--train", action="store_true",
                     help="time full training steps (forward + losses + backward + gradient all-reduce + Adam) instead "
@@ -377,8 +386,9 @@ def per_layer_table(rec, steps):
 # ------------------------------------------------------------------------------------------------------
 # measurements
 # ------------------------------------------------------------------------------------------------------
-def forward_measure(fwd, grd, sat, dev, steps, warmup, record):
-    """Times `steps` forwards; returns (max-over-ranks seconds, recorder or None)."""
+def forward_measure(fwd, grd, sat, dev, steps, warmup, record, keep_last=None):
+    """Times `steps` forwards; returns (max-over-ranks seconds, recorder or None).  keep_last: a dict that receives the
+    outputs of the last timed step as "out" (the earlier steps' outputs are dropped as they are produced)."""
     import torch
     from ccvpe_amd import harness, ops
     rec = ops.LaunchRecorder() if record else None
@@ -389,7 +399,9 @@ def forward_measure(fwd, grd, sat, dev, steps, warmup, record):
         if state["n"] == warmup:
             ops.set_recorder(rec)
         state["n"] += 1
-        fwd(grd, sat)
+        out = fwd(grd, sat)
+        if keep_last is not None and state["n"] == warmup + steps:
+            keep_last["out"] = out
 
     try:
         elapsed = harness.timed_steps(step, steps, warmup, sync_fn=torch.cuda.synchronize, device=dev)
@@ -398,10 +410,11 @@ def forward_measure(fwd, grd, sat, dev, steps, warmup, record):
     return elapsed, rec
 
 
-def train_measure(net, grd, sat, dev, batch, steps, warmup, rank, n_rot, record=False, exact_infonce=False):
+def train_measure(net, grd, sat, dev, batch, steps, warmup, rank, n_rot, record=False, exact_infonce=False, keep_last=None):
     """Times `steps` training steps as train_VIGOR.py:112-150 / train_KITTI.py:120-151 run them: ground truth, forward
     (train mode), the three losses on all levels, backward, data-parallel gradient averaging (RCCL all-reduce), Adam.
-    Returns dict(elapsed = max-over-ranks seconds, loss, peak_gib, rec, allreduce_calls_per_step, allreduce_bytes_per_step)."""
+    Returns dict(elapsed = max-over-ranks seconds, loss, peak_gib, rec, allreduce_calls_per_step, allreduce_bytes_per_step).
+    keep_last: a dict that receives the forward outputs of the last timed step as "out"."""
     import torch
     from ccvpe_amd import harness, losses, ops, optim, synth, targets
 
@@ -434,6 +447,8 @@ def train_measure(net, grd, sat, dev, batch, steps, warmup, rank, n_rot, record=
         reducer()
         opt.step()
         last["loss"] = loss.detach()
+        if keep_last is not None and state["n"] == warmup + steps:
+            keep_last["out"] = tuple(t.detach() for t in out)
 
     torch.cuda.reset_peak_memory_stats(dev)
     try:
@@ -448,9 +463,10 @@ def train_measure(net, grd, sat, dev, batch, steps, warmup, rank, n_rot, record=
                 allreduce_bytes_per_step=reducer.bytes_reduced_last_step)
 
 
-def train_entry(net, kind, grd, sat, dev, batch, steps, warmup, rank, world, n_rot, record, exact_infonce=False, tag="train"):
+def train_entry(net, kind, grd, sat, dev, batch, steps, warmup, rank, world, n_rot, record, exact_infonce=False, tag="train",
+                keep_last=None):
     """One training measurement as a JSON-able dict (value = whole-job pairs/s) + its roofline."""
-    m = train_measure(net, grd, sat, dev, batch, steps, warmup, rank, n_rot, record, exact_infonce)
+    m = train_measure(net, grd, sat, dev, batch, steps, warmup, rank, n_rot, record, exact_infonce, keep_last)
     ms = 1e3 * m["elapsed"] / steps
     out = {"workload": "%s training step (device-side ground truth, train-mode forward, loss = CE + 1e4 * mean of 6 infoNCE + "
                        "10 * orientation, backward, %sAdam lr 1e-4), batch %d per GPU, fp32"
@@ -465,6 +481,45 @@ def train_entry(net, kind, grd, sat, dev, batch, steps, warmup, rank, world, n_r
     if rank == 0:
         emit_kernel_table(tag, table)
     return out, m
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+OUTPUT_NAMES = ("logits", "heatmap", "orientation")       # then the matching-score volumes, coarsest first: score1 ... score6
+
+
+def dump_outputs(dirpath, outs, extra=None):
+    """The outputs of the last timed step as DIR/<name>.npy in float32: every output of the same fixed, seeded subset of
+    the batch (batch_index.npy names it), as many samples as fit in 64 MB (at most 8); `extra` = {name: tensor} is
+    written whole.  Same arguments -> same inputs -> comparable files across builds."""
+    import numpy as np
+    import torch
+    os.makedirs(dirpath, exist_ok=True)
+    outs = [t for t in outs if torch.is_tensor(t)]
+    names = [OUTPUT_NAMES[i] if i < len(OUTPUT_NAMES) else "score%d" % (i - len(OUTPUT_NAMES) + 1) for i in range(len(outs))]
+    extra = {k: v.detach().float().cpu().numpy().reshape(-1) for k, v in (extra or {}).items()}
+    budget = DUMP_BUDGET_BYTES - sum(v.nbytes for v in extra.values()) - (1 << 16)
+    batch = outs[0].shape[0]
+    per_sample = sum(4 * t[0].numel() for t in outs)
+    k = max(1, min(batch, 8, budget // per_sample))
+    idx = np.sort(np.random.default_rng(0).choice(batch, size=k, replace=False))
+    sel = torch.as_tensor(idx, device=outs[0].device)
+    arrays = {"batch_index": idx.astype(np.float64)}
+    for name, t in zip(names, outs):
+        a = t.detach().index_select(0, sel).float().cpu().numpy()
+        if k * per_sample > budget:          # one sample alone is over the budget: a fixed stride through each output
+            a = a.reshape(-1)[::-(-k * per_sample // budget)]
+        arrays[name] = a
+    arrays.update(extra)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirpath, name + ".npy"), np.ascontiguousarray(a))
+    return sorted(arrays)
+
+
+def param_sample(net, n=1 << 20):
+    """A fixed strided sample of n values of the concatenated parameters (the state a training step hands back)."""
+    import torch
+    flat = torch.cat([p.detach().float().reshape(-1) for p in net.parameters()])
+    return flat[::max(1, flat.numel() // n)][:n]
 
 
 def harness_active():
@@ -712,8 +767,11 @@ def main():
         if args.precision != "fp32" or args.graph:
             raise SystemExit("--train is fp32, eager only")
         n_rot = synth.MODEL_SPECS[kind]["n_rot"]
+        last = {} if args.dump_outputs else None
         entry, m = train_entry(net, kind, grd, sat, dev, args.batch, args.steps, args.warmup, rank, world, n_rot, record,
-                               args.exact_infonce)
+                               args.exact_infonce, keep_last=last)
+        if last is not None and rank == 0:
+            dump_outputs(args.dump_outputs, last.pop("out"), {"loss": torch.tensor([m["loss"]]), "params_sample": param_sample(net)})
         coll = collective_info(dev, m, world) if use_pg else None
         if rank == 0:
             line = {"metric": "train image-pairs/sec (fwd+bwd)", "value": entry["value"], "unit": "img-pairs/s", "n_gpus": world,
@@ -731,7 +789,7 @@ def main():
                 line["config"].update(flat_collective(coll))
             if m["rec"] is not None and args.per_layer:
                 per_layer_table(m["rec"], args.steps)
-            if world == 1 and not args.no_cpu_baseline and kind in ("vigor", "kitti"):
+            if args.full and world == 1 and not args.no_cpu_baseline and kind in ("vigor", "kitti"):
                 line["cpu_baseline"] = cpu_baseline_train(sd, kind)
             print(json.dumps(line))
             sys.stdout.flush()
@@ -745,7 +803,12 @@ def main():
         record = False                          # events cannot be recorded inside a replayed graph
     else:
         fwd = net
-    elapsed, rec = forward_measure(fwd, grd, sat, dev, args.steps, args.warmup, record)
+    last = {} if args.dump_outputs else None
+    elapsed, rec = forward_measure(fwd, grd, sat, dev, args.steps, args.warmup, record, keep_last=last)
+    if last is not None:
+        if rank == 0:
+            dump_outputs(args.dump_outputs, last["out"])
+        del last
 
     line = None
     if rank == 0:
@@ -788,12 +851,12 @@ def main():
         emit_kernel_table("headline", table)
         if rec is not None and args.per_layer:
             per_layer_table(rec, args.steps)
-        if world == 1 and not args.no_cpu_baseline and args.model == "prior0":
+        if args.full and world == 1 and not args.no_cpu_baseline and args.model == "prior0":
             line["cpu_baseline"] = cpu_baseline(sd)
         else:
             line["cpu_baseline"] = None
 
-    default_run = (args.model == "prior0" and args.precision == "fp32" and not args.graph and not args.no_extra)
+    default_run = (args.full and args.model == "prior0" and args.precision == "fp32" and not args.graph and not args.no_extra)
     if default_run:
         legs = {}
         want = set(args.legs.split(","))

@@ -18,7 +18,8 @@ Parity pinning: this oracle is pinned against the reference ITSELF, imported in 
 container by `tools/make_golden.py`; the resulting vectors are committed under
 `tests/golden/` (5 eval forwards, a train-mode forward with running statistics, the reference's autograd gradients
 for 520 parameter tensors, per-module outputs, losses) and re-checked by `tests/test_oracle_golden.py` everywhere, and
-`tests/test_oracle_vs_reference.py` compares live whenever /root/reference is present.
+`tests/test_oracle_vs_reference.py` checks one more forward, the state_dict layouts and the reference's datasets against
+the outputs `tools/make_golden_reference.py` stored from the reference.
 
 Every function cites the reference file:line it follows (paths under /root/reference).
 """

@@ -160,6 +160,33 @@ def load(name):
     return dict(np.load(os.path.join(GOLDEN_DIR, name + ".npz")))
 
 
+def load_json(name):
+    import json
+    with open(os.path.join(GOLDEN_DIR, name + ".json")) as f:
+        return json.load(f)
+
+
+def spread_index(n, stride):
+    """One flat index per block of `stride` elements, at a pseudo-random offset inside the block (integer hash: the same
+    on every numpy), so that a sampled comparison reaches every region of a tensor.  stride 1 = every element."""
+    j = np.arange(-(-n // stride), dtype=np.int64)
+    h = (j * 2654435761 % 4294967296) >> 16          # the high half of a multiplicative hash (its low bits repeat with period stride)
+    return np.minimum(j * stride + h % stride, n - 1)
+
+
+def digest(t):
+    """SHA-256 of a tensor's shape and VALUES (float64 image, -0.0 folded into +0.0): two arrays have the same digest
+    exactly when torch.equal / np.array_equal holds between them, whatever their storage dtypes.  The reference fixtures
+    store these for the image-sized outputs that are compared for exact equality."""
+    import hashlib
+    a = t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+    a = np.ascontiguousarray(a.astype(np.float64) + 0.0)
+    assert not np.isnan(a).any(), "NaN in a digested array"
+    h = hashlib.sha256(repr(tuple(a.shape)).encode())
+    h.update(a.tobytes())
+    return h.hexdigest()
+
+
 def assert_close(got, want, rtol, atol, what):
     got = np.asarray(got, dtype=np.float64)
     want = np.asarray(want, dtype=np.float64)

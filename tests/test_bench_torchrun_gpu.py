@@ -1,7 +1,7 @@
 """The exact launch form the SCALE driver uses — `python -m torch.distributed.run --nnodes=1 --nproc-per-node N
 --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...` — run end to end once on the one GPU a test box has
 (N = 1; the launcher starts before anything touches the GPU).  Under a launcher bench.py creates the RCCL process group and
-runs the data-parallel CVM_KITTI training leg (BASELINE configs[3]); CCVPE_ALLREDUCE_SINGLE_RANK=1 makes the 1-rank group
+runs (with --full) the data-parallel CVM_KITTI training leg (BASELINE configs[3]); CCVPE_ALLREDUCE_SINGLE_RANK=1 makes the 1-rank group
 issue the real in-place ncclAvg all-reduces of the gradient arena.  Asserted: the JSON line's flat config.collective_* fields and
 the flat config.train_dp_kitti_b64_* summary (at B = 64 per GPU: BASELINE configs[3]'s own batch); that a failure of that leg
 still prints the line, then exits non-zero; and that a --gpus / WORLD_SIZE mismatch is refused."""
@@ -26,7 +26,7 @@ def _run(extra_env, batch, gpus=1):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", CCVPE_ALLREDUCE_SINGLE_RANK="1", CCVPE_BENCH_DP_STEPS="2,2", **extra_env)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--steps", "2", "--warmup", "1",
-           "--batch", str(batch), "--legs", "dp", "--no-cpu-baseline"]
+           "--batch", str(batch), "--full", "--legs", "dp", "--no-cpu-baseline"]
     res = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=900, cwd=ROOT)
     lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
     return res, (json.loads(lines[-1]) if lines else None)

@@ -1,7 +1,8 @@
 """the host side of the VIGOR input pipeline (ccvpe_amd/datasets.py: split files -> index, PIL decode,
 the sample's orientation / positive-tile choice, sharded iteration) — CPU tests against the oracle's restatement of the
-reference dataset's arithmetic and, where /root/reference exists (the build container), against the reference's own
-`VIGORDataset.__getitem__` on the same synthetic dataset directory.  The device half (resize / normalise / roll / crop /
+reference dataset's arithmetic and against the reference's own `VIGORDataset.__getitem__` (and its KITTI / Oxford
+RobotCar datasets) on the same synthetic dataset directories, through the reference's samples stored in
+tests/golden/reference_live.json (tools/make_golden_reference.py).  The device half (resize / normalise / roll / crop /
 ground truth kernels) is in tests/test_datasets_gpu.py."""
 import os
 
@@ -11,10 +12,11 @@ import torch
 
 from ccvpe_amd import datasets as DS
 from oracle import ccvpe_oracle as O
-from ref_import import reference_available, import_reference_datasets
+import golden_util as G
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 CITIES = ("NewYork", "Seattle", "SanFrancisco", "Chicago")
+VIGOR_LIVE_SPLITS = (("samearea", False), ("crossarea", True), ("crossarea", False))
 
 
 def make_vigor_tree(root, per_city=3, sat_size=64, pano_hw=(96, 192), jpeg=True, seed=3):
@@ -119,35 +121,29 @@ def test_sample_matches_the_oracle_restatement(tmp_path):
         assert abs(peak % 512 - (256 - s["center"][0])) <= 1 and abs(peak // 512 - (256 - s["center"][1])) <= 1
 
 
-@pytest.mark.skipif(not reference_available(), reason="reference not present")
 def test_sample_matches_the_reference_dataset_live(tmp_path):
-    """The reference's own VIGORDataset on the same directory: identical sample order, orientation angle, rolled +
-    normalised panorama, aerial image and ground truth."""
-    import torch.nn.functional as F
+    """The reference's own VIGORDataset on the same directory (stored samples): identical sample order, orientation angle,
+    rolled + normalised panorama, aerial image and ground truth."""
     make_vigor_tree(str(tmp_path), jpeg=True)
-    D = import_reference_datasets()
-
-    def tf(hw):
-        return lambda im: O.preprocess_reference(np.asarray(im.convert("RGB")), hw)
+    live = G.load_json("reference_live")["vigor_splits"]
     orient = np.load(os.path.join(GOLDEN, "crossarea_orientation_test_head256.npy"))
-    for split, train in (("samearea", False), ("crossarea", True), ("crossarea", False)):
-        ref = D.VIGORDataset(str(tmp_path), split=split, train=train, transform=(tf((320, 640)), tf((512, 512))), pos_only=True,
-                             ori_noise=180, random_orientation=orient)
+    for split, train in VIGOR_LIVE_SPLITS:
+        ref = live["%s_%s" % (split, "train" if train else "test")]
         ours = DS.VIGORPairs(str(tmp_path), split=split, train=train, pos_only=True, ori_noise=180, random_orientation=orient, strict_orientation=False)
-        assert len(ours) == len(ref)
-        assert list(ours.grd_paths) == list(ref.grd_list) and list(ours.sat_paths) == list(ref.sat_list)
-        assert np.array_equal(ours.labels, ref.label) and np.array_equal(ours.deltas, ref.delta)
+        assert len(ours) == ref["len"]
+        assert list(ours.grd_paths) == [os.path.join(str(tmp_path), p) for p in ref["grd_list"]]
+        assert list(ours.sat_paths) == [os.path.join(str(tmp_path), p) for p in ref["sat_list"]]
+        assert np.array_equal(ours.labels, np.array(ref["label"])) and G.digest(ours.deltas) == ref["delta"]
         for i in range(0, len(ours), 2):
-            grd, sat, gt, gt_with_ori, orientation, city, angle = ref[i]
+            r = ref["samples"][str(i)]
             s = ours.sample(i)
-            assert s["city"] == city and abs(s["angle_deg"] - angle) < 1e-9
-            assert torch.equal(O.preprocess_reference(s["grd_u8"], (320, 640), roll=s["roll"]), grd)
-            assert torch.equal(O.preprocess_reference(s["sat_u8"], (512, 512)), sat)
+            assert s["city"] == r["city"] and abs(s["angle_deg"] - r["angle"]) < 1e-9
+            assert G.digest(O.preprocess_reference(s["grd_u8"], (320, 640), roll=s["roll"])) == r["grd"]
+            assert G.digest(O.preprocess_reference(s["sat_u8"], (512, 512))) == r["sat"]
             g, flat, ori, labs = O.train_targets([list(s["center"])], [s["angle_deg"]], 20)
-            assert torch.equal(g[0], gt) and torch.equal(ori[0], orientation)
+            assert G.digest(g[0]) == r["gt"] and G.digest(ori[0]) == r["orientation"]
             if train:
-                for k, lab in zip((64, 32, 16, 8, 4, 2), labs):
-                    assert torch.equal(lab[0], F.max_pool2d(gt_with_ori[None], k, stride=k)[0])
+                assert [G.digest(lab[0]) for lab in labs] == r["gt_with_ori_pooled"]
 
 
 def test_device_batches_shard_without_overlap(tmp_path):
@@ -285,42 +281,34 @@ def test_kitti_index_paths_and_listed_perturbations(tmp_path):
     assert a == b and all(-1 <= v <= 1 for v in a[:2]) and abs(a[2]) <= 10
 
 
-@pytest.mark.skipif(not reference_available(), reason="reference not present")
+def kitti_center_crop(img, size):
+    """torchvision 0.x's `TF.center_crop` rule on a PIL image (top/left = int(round((size - crop) / 2))): the reference's one
+    use of torchvision in its KITTI datasets, supplied where the fixture is made (torchvision is not installed there)."""
+    w, h = img.size
+    left, top = int(round((w - size) / 2.0)), int(round((h - size) / 2.0))
+    return img.crop((left, top, left + size, top + size))
+
+
 def test_kitti_sample_matches_the_reference_datasets_live(tmp_path):
-    """The reference's own SatGrdDataset / SatGrdDatasetTest on the same directory: the aligned + perturbed aerial crop, the camera
-    image, the orientation angle and — through the oracle's ground-truth restatement with 16 bins — gt, gt_with_ori (max-pooled)
-    and the orientation map.  torchvision is not installed in this image: the reference's one use of it here,
-    `TF.center_crop` on a PIL image, is supplied with torchvision 0.x's published rule (top/left = int(round((size - crop) / 2)))."""
-    import torch.nn.functional as F
+    """The reference's own SatGrdDataset / SatGrdDatasetTest on the same directory (stored samples): the aligned + perturbed
+    aerial crop, the camera image, the orientation angle and — through the oracle's ground-truth restatement with 16 bins —
+    gt, gt_with_ori (max-pooled) and the orientation map."""
     train_file, test_file, names = make_kitti_tree(str(tmp_path))
-    D = import_reference_datasets()
-
-    def center_crop(img, size):
-        w, h = img.size
-        left, top = int(round((w - size) / 2.0)), int(round((h - size) / 2.0))
-        return img.crop((left, top, left + size, top + size))
-    D.TF.center_crop = center_crop
-
-    def to_u8(im):
-        return torch.from_numpy(np.array(im)).permute(2, 0, 1)
+    live = G.load_json("reference_live")["kitti"]
     for test in (False, True):
-        cls = D.SatGrdDatasetTest if test else D.SatGrdDataset
-        ref = cls(str(tmp_path), test_file if test else train_file, transform=(to_u8, to_u8), shift_range_lat=20, shift_range_lon=20,
-                  rotation_range=(10 if test else 180))
+        ref = live["test" if test else "train"]
         ours = DS.KITTIPairs(str(tmp_path), test_file if test else train_file, 20, 20, 10 if test else 180, test=test)
-        assert len(ours) == len(ref)
+        assert len(ours) == ref["len"]
         for i in range(len(ours)):
-            np.random.seed(100 + i)
-            sat, grd, gt, gt_with_ori, orientation, angle = ref[i]
+            r = ref["samples"][i]
             np.random.seed(100 + i)
             s = ours.sample(i)
-            assert abs(s["angle_deg"] - angle) < 1e-9
-            assert np.array_equal(s["sat_u8"], sat.permute(1, 2, 0).numpy())
-            assert np.array_equal(s["grd_u8"].astype(np.float32), grd.permute(1, 2, 0).numpy().astype(np.float32))
+            assert abs(s["angle_deg"] - r["angle"]) < 1e-9
+            assert G.digest(s["sat_u8"]) == r["sat"]
+            assert G.digest(s["grd_u8"].astype(np.float32)) == r["grd"]
             g, flat, ori, labs = O.train_targets([list(s["center"])], [s["angle_deg"]], 16)
-            assert torch.equal(g[0], gt) and torch.equal(ori[0], orientation)
-            for k, lab in zip((64, 32, 16, 8, 4, 2), labs):
-                assert torch.equal(lab[0], F.max_pool2d(gt_with_ori[None], k, stride=k)[0])
+            assert G.digest(g[0]) == r["gt"] and G.digest(ori[0]) == r["orientation"]
+            assert [G.digest(lab[0]) for lab in labs] == r["gt_with_ori_pooled"]
 
 
 # ---- Oxford RobotCar ----------------------------------------------------------------------------------------------------
@@ -364,35 +352,26 @@ def test_oxford_index_and_grid_patches(tmp_path):
     assert max(np.hypot(a, b) for a, b in offs) <= 200 * np.sqrt(2) and len(set(offs)) > 150
 
 
-@pytest.mark.skipif(not reference_available(), reason="reference not present")
 def test_oxford_sample_matches_the_reference_dataset_live(tmp_path):
-    """The reference's OxfordRobotCarDataset on the same directory (Python's `random` seeded identically on both sides): camera
-    image, the 800 x 800 map patch, orientation angle and — through the oracle's restatement with ASCENDING bins — gt, gt_with_ori
-    (max-pooled) and the orientation map."""
+    """The reference's OxfordRobotCarDataset on the same directory (stored samples; Python's `random` seeded identically on
+    both sides): camera image, the 800 x 800 map patch (resized to the 512 x 512 the reference's transform was given),
+    orientation angle and — through the oracle's restatement with ASCENDING bins — gt, gt_with_ori (max-pooled) and the
+    orientation map."""
     import random
-    import torch.nn.functional as F
+    from PIL import Image
     g, sat_path = make_oxford_tree(str(tmp_path))
-    D = import_reference_datasets()
-
-    def to_u8(im):
-        return torch.from_numpy(np.array(im.convert("RGB"))).permute(2, 0, 1)
-
-    def to_512(im):          # the reference reads the ground-truth size from the transformed aerial image: give it 512 x 512
-        return torch.from_numpy(np.array(im.convert("RGB").resize((512, 512)))).permute(2, 0, 1)
+    live = G.load_json("reference_live")["oxford"]
     for split in ("train", "val", "test"):
-        ref = D.OxfordRobotCarDataset(g, sat_path, split=split, transform=(to_u8, to_512))
+        ref = live[split]
         ours = DS.OxfordPairs(g, sat_path, split=split)
-        assert len(ours) == len(ref)
+        assert len(ours) == ref["len"]
         for i in range(len(ours)):
-            random.seed(50 + i)
-            grd, sat, gt, gt_with_ori, orientation, angle = ref[i]
+            r = ref["samples"][i]
             random.seed(50 + i)
             s = ours.sample(i)
-            assert abs(s["angle_deg"] - angle) < 1e-9
-            assert np.array_equal(s["grd_u8"], grd.permute(1, 2, 0).numpy())
-            from PIL import Image
-            assert np.array_equal(np.array(Image.fromarray(s["sat_u8"]).resize((512, 512))), sat.permute(1, 2, 0).numpy())
+            assert abs(s["angle_deg"] - r["angle"]) < 1e-9
+            assert G.digest(s["grd_u8"]) == r["grd"]
+            assert G.digest(np.array(Image.fromarray(s["sat_u8"]).resize((512, 512)))) == r["sat"]
             gg, flat, ori, labs = O.train_targets([list(s["center"])], [s["angle_deg"]], 20, ascending=True)
-            assert torch.equal(gg[0], gt) and torch.equal(ori[0], orientation)
-            for k, lab in zip((64, 32, 16, 8, 4, 2), labs):
-                assert torch.equal(lab[0], F.max_pool2d(gt_with_ori[None], k, stride=k)[0])
+            assert G.digest(gg[0]) == r["gt"] and G.digest(ori[0]) == r["orientation"]
+            assert [G.digest(lab[0]) for lab in labs] == r["gt_with_ori_pooled"]

@@ -1,7 +1,7 @@
 """Import the upstream CCVPE reference (read-only, /root/reference) in THIS container.
 
-Test/fixture infrastructure only: used by tools/make_golden.py and the `-m "not gpu"`
-oracle-vs-reference tests when /root/reference exists. Never imported by the product
+Fixture infrastructure only: used by tools/make_golden.py and tools/make_golden_reference.py
+(no test imports it: the tests read what they stored). Never imported by the product
 (ccvpe_amd/) and never available on the GPU box.
 
 Two shims:
