@@ -82,6 +82,8 @@ PROTOTYPES = {
     "ccvpe_mbconv_front_route": (c_int, [c_int] * 8),
     "ccvpe_set_match_mfma": (c_int, [c_int]),
     "ccvpe_set_pwn_kernels": (c_int, [c_int]),
+    "ccvpe_conv3x3_wino_ok": (c_int, [ctypes.POINTER(ConvDesc)]),
+    "ccvpe_conv3x3_wino_f32": (c_int, [ctypes.POINTER(ConvDesc), c_void_p]),
     "ccvpe_conv3x3_match1_ok": (c_int, [ctypes.POINTER(ConvDesc), c_int, c_int]),
     "ccvpe_conv3x3_match1_bf16": (c_int, [ctypes.POINTER(ConvDesc), c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "ccvpe_conv_igemm_splitk_f32": (c_int, [ctypes.POINTER(ConvDesc), c_void_p, c_void_p]),

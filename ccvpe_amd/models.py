@@ -87,6 +87,23 @@ def _pack_conv(w, dtype=torch.float32):
     return _pad2(w.permute(0, 2, 3, 1).reshape(o, -1), dtype)
 
 
+# Winograd F(2x2,3x3) filter transform: U = G g G^T (csrc/conv3x3_wino.hip)
+_WINO_G = ((1.0, 0.0, 0.0), (0.5, 0.5, 0.5), (0.5, -0.5, 0.5), (0.0, 0.0, 1.0))
+
+
+def _pack_wino(w, dtype=torch.float32):
+    """OIHW 3x3 -> the transformed weights of ccvpe_conv3x3_wino_f32: U = G g G^T in fp64, rounded once to fp32, packed
+    [round_up(O, 32)][16 components][round_up(I, 16)] (zero-padded).  None for bf16 packs (the kernel is fp32 only)."""
+    if dtype != torch.float32:
+        return None
+    o, i = w.shape[0], w.shape[1]
+    g = torch.tensor(_WINO_G, dtype=torch.float64, device=w.device)
+    u = torch.einsum("ak,ockl,bl->oabc", g, w.to(torch.float64), g)          # [O][4][4][I]
+    out = torch.zeros((_round_up(o, 32), 4, 4, _round_up(i, 16)), dtype=torch.float64, device=w.device)
+    out[:o, :, :, :i] = u
+    return out.reshape(out.shape[0], -1).to(torch.float32).contiguous()
+
+
 def _fold_bn(sd, p):
     scale = sd[p + ".weight"] / torch.sqrt(sd[p + ".running_var"] + BN_EPS)
     shift = sd[p + ".bias"] - sd[p + ".running_mean"] * scale
@@ -168,6 +185,8 @@ FOLD_MIN_PIXELS = int(__import__("os").environ.get("CCVPE_FOLD_MIN_PIXELS", "204
 FUSE_TAIL = __import__("os").environ.get("CCVPE_FUSE_TAIL", "1") != "0"
 # bf16 storage path: the fp32 tail's matrix arithmetic on bf16 hi + lo planes (csrc/tail512.hip SPLIT); CCVPE_SPLIT_TAIL=0 = exact fp32
 SPLIT_TAIL = __import__("os").environ.get("CCVPE_SPLIT_TAIL", "1") != "0"
+# fp32 convK.2 layers by Winograd F(2x2,3x3) where the library serves the shape (csrc/conv3x3_wino.hip); CCVPE_WINO=0 = direct (A/B runs)
+WINO = __import__("os").environ.get("CCVPE_WINO", "1") != "0"
 # train mode: replay the per-step weight re-pack as one hipGraph (see _CVMBase._packed); CCVPE_PACK_GRAPH=0 keeps it eager
 PACK_GRAPH = __import__("os").environ.get("CCVPE_PACK_GRAPH", "1") != "0"
 # train mode, fp32: the per-step re-pack as ONE gather launch (ccvpe_amd/repack.py); CCVPE_PACK_GATHER=0 keeps the graph replay
@@ -326,6 +345,7 @@ def _pack_model(sd, kind, n_tail, dtype=torch.float32, fold=True, f32_tail=0):
         lv.b_a = sd["conv%d.0.bias" % lvl].contiguous()
         if lvl != 1:
             lv.w_b = _pack_conv(sd["conv%d.2.weight" % lvl], dtype)
+            lv.u_b = _pack_wino(sd["conv%d.2.weight" % lvl], base_dtype) if fold else None
             lv.n_b = c_out
         else:
             lv.w_b = sd["conv1.2.weight"].permute(0, 2, 3, 1).contiguous()      # [1][3][3][16]
@@ -358,6 +378,7 @@ def _pack_model(sd, kind, n_tail, dtype=torch.float32, fold=True, f32_tail=0):
         ov.n_a = c_out
         if lvl != 1:
             ov.w_b = _pack_conv(sd["conv%d_ori.2.weight" % lvl], dtype)
+            ov.u_b = _pack_wino(sd["conv%d_ori.2.weight" % lvl], dtype) if fold else None
             ov.n_b = c_out
         else:
             ov.w_b = sd["conv1_ori.2.weight"].permute(0, 2, 3, 1).contiguous()  # [2][3][3][16]
@@ -413,6 +434,16 @@ def _double_conv(lv, up, skip, batch, hw):
     y = ops.conv_igemm(up, lv.c0, lv.w_a, lv.n_a, batch=batch, in_h=hw, in_w=hw, kh=3, kw=3, pad=1,
                        src1=skip, c1=lv.c1, shift=lv.b_a, act=ops.ACT_RELU)
     return y
+
+
+def _conv_b(lv, y, batch, hw, out_f32=False):
+    """convK.2 of double_conv (3x3, bias, no activation): Winograd F(2x2,3x3) where the library serves the layer (fp32
+    storage, csrc/conv3x3_wino.hip), else the direct 3x3 kernel."""
+    if (WINO and lv.u_b is not None and
+            ops.conv3x3_wino_ok(y, lv.n_a, lv.u_b, lv.n_b, batch=batch, in_h=hw, in_w=hw)):
+        return ops.conv3x3_wino(y, lv.n_a, lv.u_b, lv.n_b, batch=batch, in_h=hw, in_w=hw, shift=lv.b_b)
+    return ops.conv_igemm(y, lv.n_a, lv.w_b, lv.n_b, batch=batch, in_h=hw, in_w=hw, kh=3, kw=3, pad=1, shift=lv.b_b,
+                          out_f32=out_f32)
 
 
 class _CVMBase(nn.Module):
@@ -579,8 +610,7 @@ class _CVMBase(nn.Module):
                                     shift=ov.up_b, out_mode=ops.OUT_DECONV2X, algo_k=ov.k_algo)
                 y = _double_conv(ov, up, skip, batch, 2 * hw)
             if j < 5:
-                xo = ops.conv_igemm(y, ov.n_a, ov.w_b, ov.n_b, batch=batch, in_h=2 * hw, in_w=2 * hw,
-                                    kh=3, kw=3, pad=1, shift=ov.b_b)
+                xo = _conv_b(ov, y, batch, 2 * hw)
             else:
                 return ops.head_conv3x3(y, ov.w_b, ov.b_b, 2, normalize)       # + F.normalize (:341)
 
@@ -734,8 +764,7 @@ class _CVMBase(nn.Module):
                                                    window_offset=window_offset(self.kind, nxt.c, L_n), out_f32=to_f32)
                         x = fused[1]                 # (only its shape is read at the top of the next level)
                     else:
-                        x = ops.conv_igemm(y, lv.n_a, lv.w_b, lv.n_b, batch=batch, in_h=2 * hw, in_w=2 * hw,
-                                           kh=3, kw=3, pad=1, shift=lv.b_b, out_f32=to_f32)
+                        x = _conv_b(lv, y, batch, 2 * hw, out_f32=to_f32)
                 else:
                     logits_map = ops.head_conv3x3(y, lv.w_b, lv.b_b, 1, False)      # [B,1,512,512]
             logits = logits_map.reshape(batch, -1)                                   # models.py:319

@@ -227,6 +227,53 @@ def conv_igemm(src0, c0, w_packed, n, *, batch, in_h, in_w, kh=1, kw=1, stride=1
     return dst
 
 
+def _wino_desc(src0, c0, u_packed, n, batch, in_h, in_w, shift, dst, ldd, ld0):
+    d = ConvDesc()
+    d.src0, d.src1, d.gate, d.w = _ptr(src0), None, None, _ptr(u_packed)
+    d.scale, d.shift, d.residual, d.dst = None, _ptr(shift), None, _ptr(dst) if dst is not None else None
+    d.c0, d.ld0, d.c1, d.ld1 = c0, ld0, 0, 0
+    d.batch, d.in_h, d.in_w = batch, in_h, in_w
+    d.kh, d.kw, d.stride, d.pad = 3, 3, 1, 1
+    d.n, d.kpad = n, u_packed.shape[1]
+    d.ldd, d.ldres = ldd, 0
+    d.act, d.out_mode = ACT_NONE, OUT_NHWC
+    return d
+
+
+def conv3x3_wino_ok(src0, c0, u_packed, n, *, batch, in_h, in_w, ldd=None, ld0=None):
+    """True if ccvpe_conv3x3_wino_f32 serves this layer (fp32 storage and the library's own shape rules)."""
+    if src0.dtype != torch.float32 or u_packed is None:
+        return False
+    ld0 = ld0 if ld0 is not None else src0.shape[-1]
+    d = _wino_desc(src0, c0, u_packed, n, batch, in_h, in_w, None, None, ldd if ldd is not None else n, ld0)
+    return bool(_lib.load().ccvpe_conv3x3_wino_ok(ctypes.byref(d)))
+
+
+def conv3x3_wino(src0, c0, u_packed, n, *, batch, in_h, in_w, shift=None, dst=None, ldd=None, ld0=None):
+    """fp32 3x3 / stride 1 / pad 1 conv with bias by Winograd F(2x2,3x3) (ccvpe_conv3x3_wino_f32); u_packed from
+    models._pack_wino.  Same result as conv_igemm(..., kh=3, kw=3, pad=1, shift=shift) to fp32 rounding, not bit for bit."""
+    lib = _lib.load()
+    for t, nm in ((src0, "src0"), (u_packed, "w"), (shift, "shift"), (dst, "dst")):
+        _chk(t, nm)
+    ld0 = ld0 if ld0 is not None else src0.shape[-1]
+    if dst is None:
+        ldd = ldd if ldd is not None else n
+        dst = _empty((batch, in_h, in_w, ldd), device=src0.device)
+    elif ldd is None:
+        ldd = dst.shape[-1]
+    d = _wino_desc(src0, c0, u_packed, n, batch, in_h, in_w, shift, dst, ldd, ld0)
+    rec = _recorder
+    ev0 = rec.begin() if rec is not None else None
+    check(lib.ccvpe_conv3x3_wino_f32(ctypes.byref(d), _stream()), "ccvpe_conv3x3_wino_f32")
+    if rec is not None:
+        m = batch * in_h * in_w
+        # the direct algorithm's FLOPs (BASELINE.md): the "TF" of this kernel in the bench tables can exceed the fp32 peak
+        flops = 2.0 * m * n * 9 * c0
+        nbytes = 4.0 * (m * c0 + m * n + n * 9 * c0)
+        rec.end("conv3x3_wino_f32_kernel<16x16,32>", "3x3 s1 M%d N%d K%d" % (m, n, 9 * c0), flops, nbytes, ev0)
+    return dst
+
+
 def upconv3x3(src0, c0, w_packed, shift9, n, *, batch, h1, w1, src1=None, c1=0, act=ACT_NONE, algo_flops=None, route_only=False):
     """ConvTranspose2d(k2,s2) folded into the following 3x3 conv (ccvpe_upconv3x3_f32 / _bf16).
     src0 [B,h1,w1,ld0] low-res, src1 [B,2h1,2w1,ld1] skip; returns [B,2h1,2w1,n]."""

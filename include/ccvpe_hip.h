@@ -125,6 +125,13 @@ int ccvpe_set_mbconv_plane_kernels(int mode);
  * bf16, or fp32 with out_f32), scores [B,1,H,W] fp32; g [B][ldg] fp32 ground descriptor (first L entries), shift / stride /
  * window_offset as ccvpe_match_level.  Same formulas as ccvpe_match_level (no eps in the cosine).  _ok: 1 if the library serves
  * this layer / shape (narrow-level kernel, csrc/narrow_impl.h), else 0 — then run the two calls separately. */
+/* fp32 3x3 layer (stride 1, pad 1, one source, bias only: convK.2 of double_conv, models.py:42-47) by Winograd F(2x2,3x3)
+ * (csrc/conv3x3_wino.hip).  desc as for ccvpe_conv_igemm_f32 except `w`: the transformed weights U = G g G^T, packed
+ * [round_up(n, 32)][16][round_up(c0, 16)] (row = output channel; component xi = 4 * row + column of the 4 x 4 grid, then
+ * input channel; zero-padded), and kpad = 16 * round_up(c0, 16).  _ok: 1 if the kernel serves `desc` (H and W even,
+ * c0 >= 32, batch * H * W >= 16384, not a shape the direct path splits along K), else 0 — then use ccvpe_conv_igemm_f32. */
+int ccvpe_conv3x3_wino_ok(const ccvpe_conv_desc* desc);
+int ccvpe_conv3x3_wino_f32(const ccvpe_conv_desc* desc, void* stream);
 int ccvpe_conv3x3_match1_ok(const ccvpe_conv_desc* desc, int out_f32, int L);
 int ccvpe_conv3x3_match1_bf16(const ccvpe_conv_desc* desc, int out_f32, const float* g, int ldg, int L, int shift, int stride,
                               int window_offset, float* scores, void* stream);
