@@ -246,3 +246,36 @@ def test_pw_ring_is_never_routed_with_fewer_than_three_k_stages():
     assert fam(lib.ccvpe_conv_igemm_route(ctypes.byref(d), 0, 0)) == 4        # fp32 K = 64: four stages
     d.c0, d.ld0, d.kpad = 48, 48, 48
     assert fam(lib.ccvpe_conv_igemm_route(ctypes.byref(d), 0, 0)) == 1        # fp32 K = 48 (three stages): below the ring's minimum K
+
+
+def test_fullsize_train_kernel_table_matches_the_geometry_queries():
+    """Host-only: every row of tests/train_kernel_shapes.py (the shapes tests/test_fullsize_train_kernels_gpu.py checks against
+    float64) still takes the branch it is there for — a routing change fails here, without a GPU, instead of silently moving a
+    row onto an easier path."""
+    import train_kernel_shapes as S
+    lib = _lib.load()
+    for name, rows, c, rpb, nblk in S.BN_STATS:
+        assert lib.ccvpe_bn_stats_nblk(rows) == nblk, name
+        parts = (rows + rpb - 1) // rpb                                     # partial rows, then one fold row per 64
+        assert parts + (parts + 63) // 64 == nblk, "%s: rows per workgroup is no longer %d" % (name, rpb)
+    for name, b, rps, c, act, dcs, nblk in S.BN_ACT:
+        assert lib.ccvpe_bn_act_nblk(rps) == nblk and lib.ccvpe_bn_bwd_nblk(rps) == nblk, name
+    for name, b, h, w, c, cs, nblk in S.BN_SE:
+        assert lib.ccvpe_bn_act_nblk(h * w) == nblk and lib.ccvpe_bn_bwd_nblk(h * w) == nblk, name
+    for name, b, h, w, c, k, s, circ, nblk in S.DW_WGRAD:
+        assert h * w > 1024, "%s: not the all-taps kernel" % name
+        assert lib.ccvpe_dwconv_wgrad_nblk(h, w, k, s) == nblk, name
+    for name, b, h, w, cout, ntiles in S.HEAD_BWD:
+        assert ((w + 63) // 64) * ((h + 3) // 4) * b == ntiles > S.HEAD_WGRAD_BLOCKS, name
+    for name, b, h, w, circ, nblk, partial in S.STEM_WGRAD:
+        assert lib.ccvpe_stem_wgrad_nblk(b, h, w) == nblk, name
+        assert ((w // 2) % 256 != 0) == partial, name
+    for name, b, c, L, side, shifts, n_max, n_tail, stride, nblk, npad in S.MATCH_BWD:
+        assert lib.ccvpe_match_bwd_nblk(side * side, b, c) == nblk, name
+        assert S.npad_of(len(shifts)) == npad, name
+    lds = {name: S.match_bwd_lds_bytes(c, L, side * side, len(shifts), npad)
+           for name, b, c, L, side, shifts, n_max, n_tail, stride, nblk, npad in S.MATCH_BWD}
+    assert sum(v > 64 * 1024 for v in lds.values()) >= 2 and max(lds.values()) <= 160 * 1024, lds
+    assert any(row[-1] == 48 for row in S.MATCH_BWD) and any(row[-2] == 32 for row in S.MATCH_BWD)   # NPAD 48, 32 slices
+    for name, rows, c, ld in S.COLSUM:
+        assert rows >= S.CS_ROWS * 256, "%s: not the many-rows branch" % name

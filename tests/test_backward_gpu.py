@@ -91,7 +91,8 @@ def _act(z, act):
 
 @pytest.mark.parametrize("c,h,w,act,with_se,with_dcs", [(32, 20, 24, 2, True, False), (96, 9, 7, 2, False, True),
                                                         (40, 5, 6, 0, False, True), (1152, 3, 4, 2, True, False),
-                                                        (16, 33, 17, 1, False, False)])
+                                                        (16, 33, 17, 1, False, False), (56, 7, 9, 2, True, False),
+                                                        (1280, 3, 5, 2, False, True)])
 def test_bn_act_bwd_vs_autograd(bw, c, h, w, act, with_se, with_dcs):
     from ccvpe_amd import ops
     b, eps = 4, 1e-3
@@ -302,7 +303,9 @@ def test_stem_wgrad(bw, circ):
     (64, 64, 12, list(range(20)), 20, 0, 2),
     (32, 20, 16, [-1, 0, 1], 3, 0, 4),                       # partial window (FoV < 360), ori_prior shifts
     (128, 128, 5, [0] + list(range(20)), 1, 20, 4),          # ori_prior level 6: 1 loc shift + 20 recomputed
-    (16, 10, 40, list(range(16)), 16, 0, 8)])                # kitti-like, hw > 256 pixels per sample
+    (16, 10, 40, list(range(16)), 16, 0, 8),                 # kitti-like, hw > 256 pixels per sample
+    (320, 320, 16, list(range(20)), 20, 0, 16),              # 68.7 KB of LDS: the hipFuncSetAttribute launch (VIGOR level 2)
+    (64, 64, 6, list(range(-8, 9)) + list(range(20)), 17, 20, 2)])   # 37 shifts: NPAD = 48 (ori_prior with ori_noise >= 72)
 def test_match_level_bwd_vs_autograd(bw, c, L, hw, shifts, n_max, n_tail, stride):
     from ccvpe_amd import ops
     from oracle import ccvpe_oracle as orc

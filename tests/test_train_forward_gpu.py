@@ -26,7 +26,8 @@ def close(got, want, tol, what):
     assert err <= tol * scale, "%s: max err %.3e vs scale %.3e" % (what, err, scale)
 
 
-@pytest.mark.parametrize("b,h,w,c", [(2, 9, 13, 96), (3, 16, 16, 1152), (2, 40, 72, 32), (1, 5, 7, 24)])
+@pytest.mark.parametrize("b,h,w,c", [(2, 9, 13, 96), (3, 16, 16, 1152), (2, 40, 72, 32), (1, 5, 7, 24),
+                                     (2, 48, 40, 56), (1, 8, 9, 1280)])       # C % 16 != 0 (fold lane mask); C > 1 024
 def test_bn_stats_and_running_update(ops, b, h, w, c):
     x = synth.normal((b, h, w, c), 700 + c, 1.7) + synth.normal((c,), 701, 2.0)      # non-zero channel means
     rm, rv = synth.normal((c,), 702, 0.3), synth.uniform((c,), 703, 0.5, 1.5)
