@@ -80,6 +80,8 @@ PROTOTYPES = {
     "ccvpe_set_pw_ring_kernels": (c_int, [c_int]),
     "ccvpe_set_mbconv_plane_kernels": (c_int, [c_int]),
     "ccvpe_mbconv_front_route": (c_int, [c_int] * 8),
+    "ccvpe_mbconv_band_plan": (c_int, [c_int] * 7),
+    "ccvpe_conv3x3_variant": (c_int, [ctypes.POINTER(ConvDesc), c_int]),
     "ccvpe_set_match_mfma": (c_int, [c_int]),
     "ccvpe_set_pwn_kernels": (c_int, [c_int]),
     "ccvpe_conv3x3_wino_ok": (c_int, [ctypes.POINTER(ConvDesc)]),

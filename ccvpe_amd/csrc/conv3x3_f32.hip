@@ -2,4 +2,5 @@
 #include "conv3x3_impl.h"
 namespace ccvpe {
 template int conv3x3_dispatch<float>(const IgemmParams&, int, int, int, int, hipStream_t);
+template int conv3x3_variant_query<float>(const IgemmParams&, int, int, int, int);
 }

@@ -519,8 +519,47 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wreg_kernel(const IgemmParams 
 
 #endif  // CCVPE_ABLATE
 
+// ---- which form of conv3x3_kernel a <MT, NT, WN> tile runs: ONE decision, read by the launchers below and by
+// ccvpe_conv3x3_variant (tests assert the form of a row before they launch it) -----------------------------------------------
+// 8 waves are instantiated only for the wide-N tiles that dominate the decoder
+// (fp32, NT = 5 needs > 128 VGPRs: with the 4-waves/SIMD cap it spills (121 -> 88 TF); uncapped at one
+// workgroup per CU it reaches 119 TF vs 122.5 for the 4-wave form, so only NT = 4 uses 8 waves)
+template <typename T, int NT, int WN>
+constexpr bool conv3_has_nw8() { return WN == 2 && (NT == 4 || (NT == 5 && sizeof(T) == 2)); }
+// a row of taps per stage for the 4-wave form (the fp32 8-wave form lives under a 128-VGPR cap: no room for the second fragment
+// set) (256 x 80 tile: a row of taps per stage measured the same, 117.8 vs 117.0 TF)
+template <typename T, int NT, int WN, int NW>
+constexpr bool conv3_row_stage() { return (NW == 4 || sizeof(T) == 2) && !(NT == 5 && WN == 1); }
+
+// NW | DMA << 4 | TPS << 8
+template <typename T, int MT, int NT, int WN>
+static int conv3x3_variant(const IgemmParams& p0, int batch) {
+  constexpr int BN = 16 * NT * WN;
+  int nw = 4;
+  if constexpr (conv3_has_nw8<T, NT, WN>()) {
+    constexpr int TH8 = 16 * MT * (8 / WN) / 16;
+    const long tiles_n = (p0.Npad + BN - 1) / BN;
+    const long blocks8 = (long)((p0.W + 15) / 16) * ((p0.H + TH8 - 1) / TH8) * batch * tiles_n;
+    if constexpr (sizeof(T) == 4) {
+      // fp32: 8 waves (256-pixel tile) when the image is tall enough for the 2x taller tile and the grid still has
+      // >= 2 workgroups per CU
+      if (g_conv3_nw8 && p0.H % TH8 == 0 && blocks8 >= 512) nw = 8;
+    } else {
+      // bf16: 8 waves share one W panel and one halo (256-pixel tile, a row of taps per stage, one workgroup per CU, no VGPR cap).
+      // Round 4, isolated layers at B = 64 (tools/gpu/ab_c3.sh): 640 -> 640 at 16 x 16 885 -> 916 TF, 320 -> 320 at 32 x 32 832 -> 870,
+      // 1344 -> 640 875 -> 920; 160 -> 160 at 64 x 64 (ONE column tile) 757 -> 734: only layers with >= 2 column tiles take it.
+      if (p0.H % TH8 == 0 && blocks8 >= 256 && tiles_n >= 2) nw = 8;
+    }
+  }
+  // W by LDS-DMA when the tile is fully inside the packed rows (no row guard possible)
+  const bool dma = p0.Npad % BN == 0;
+  const bool row = nw == 8 ? conv3_row_stage<T, NT, WN, 8>() : conv3_row_stage<T, NT, WN, 4>();
+  const int tps = (dma && row && g_conv3_tps == 3) ? 3 : 1;
+  return nw | ((dma ? 1 : 0) << 4) | (tps << 8);
+}
+
 template <typename T, int MT, int NT, int WN, int NW>
-static int launch3x3_nw(const IgemmParams& p0, int batch, hipStream_t stream) {
+static int launch3x3_nw(const IgemmParams& p0, int batch, int variant, hipStream_t stream) {
   constexpr int WM = NW / WN;
   constexpr int BM = 16 * MT * WM;
   constexpr int BN = 16 * NT * WN;
@@ -543,22 +582,22 @@ static int launch3x3_nw(const IgemmParams& p0, int batch, hipStream_t stream) {
     }
   }
 #endif
-  // W by LDS-DMA when the tile is fully inside the packed rows (no row guard possible), a row of taps per stage for the
-  // 4-wave form (the 8-wave form lives under a 128-VGPR cap: no room for the second fragment set)
   static bool attr_set[3] = {false, false, false};      // per (T, tile) instantiation of this launcher: one flag per kernel variant
-  auto go = [&](int variant, void (*kern)(const IgemmParams), int lds) -> int {
-    if (!attr_set[variant] && lds > 48 * 1024) {
+  auto go = [&](int slot, void (*kern)(const IgemmParams), int lds) -> int {
+    if (!attr_set[slot] && lds > 48 * 1024) {
       hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
       if (e != hipSuccess) return fail(CCVPE_ELAUNCH, "conv3x3: set smem attr: %s", hipGetErrorString(e));
-      attr_set[variant] = true;
+      attr_set[slot] = true;
     }
     hipLaunchKernelGGL(kern, dim3(p.tiles_total), dim3(64 * NW), lds, stream, p);
     return CCVPE_OK;
   };
+  const bool dma = (variant >> 4) & 1;                  // conv3x3_variant(): the form is decided there, only instantiated here
+  const int tps = variant >> 8;
   int rc;
-  if (p.Npad % BN == 0) {
-    if constexpr ((NW == 4 || sizeof(T) == 2) && !(NT == 5 && WN == 1)) {      // (256 x 80 tile: a row of taps per stage measured the same, 117.8 vs 117.0 TF)
-      if (g_conv3_tps == 3) rc = go(0, conv3x3_kernel<T, MT, NT, WN, NW, true, 3>, Conv3Geom<T, MT, NT, WN, NW, true, 3>::LDS_BYTES);
+  if (dma) {
+    if constexpr (conv3_row_stage<T, NT, WN, NW>()) {
+      if (tps == 3) rc = go(0, conv3x3_kernel<T, MT, NT, WN, NW, true, 3>, Conv3Geom<T, MT, NT, WN, NW, true, 3>::LDS_BYTES);
       else rc = go(1, conv3x3_kernel<T, MT, NT, WN, NW, true, 1>, Conv3Geom<T, MT, NT, WN, NW, true, 1>::LDS_BYTES);
     } else {
       rc = go(1, conv3x3_kernel<T, MT, NT, WN, NW, true, 1>, Conv3Geom<T, MT, NT, WN, NW, true, 1>::LDS_BYTES);
@@ -572,27 +611,11 @@ static int launch3x3_nw(const IgemmParams& p0, int batch, hipStream_t stream) {
 
 template <typename T, int MT, int NT, int WN>
 static int launch3x3(const IgemmParams& p0, int batch, hipStream_t stream) {
-  // 8 waves (256-pixel tile) when the image is tall enough for the 2x taller tile and the grid still has
-  // >= 2 workgroups per CU; only instantiated for the wide-N tiles that dominate the decoder
-  // (NT = 5 needs > 128 VGPRs: with the 4-waves/SIMD cap it spills (121 -> 88 TF); uncapped at one
-  // workgroup per CU it reaches 119 TF vs 122.5 for the 4-wave form, so only NT = 4 uses 8 waves)
-  if constexpr (WN == 2 && NT == 4 && sizeof(T) == 4) {
-    constexpr int TH8 = 16 * MT * (8 / WN) / 16;
-    constexpr int BN = 16 * NT * WN;
-    const long blocks8 = (long)((p0.W + 15) / 16) * ((p0.H + TH8 - 1) / TH8) * batch * ((p0.Npad + BN - 1) / BN);
-    if (g_conv3_nw8 && p0.H % TH8 == 0 && blocks8 >= 512) return launch3x3_nw<T, MT, NT, WN, 8>(p0, batch, stream);
+  const int variant = conv3x3_variant<T, MT, NT, WN>(p0, batch);
+  if constexpr (conv3_has_nw8<T, NT, WN>()) {
+    if ((variant & 15) == 8) return launch3x3_nw<T, MT, NT, WN, 8>(p0, batch, variant, stream);
   }
-  if constexpr (WN == 2 && (NT == 4 || NT == 5) && sizeof(T) == 2) {
-    // bf16: 8 waves share one W panel and one halo (256-pixel tile, a row of taps per stage, one workgroup per CU, no VGPR cap).
-    // Round 4, isolated layers at B = 64 (tools/gpu/ab_c3.sh): 640 -> 640 at 16 x 16 885 -> 916 TF, 320 -> 320 at 32 x 32 832 -> 870,
-    // 1344 -> 640 875 -> 920; 160 -> 160 at 64 x 64 (ONE column tile) 757 -> 734: only layers with >= 2 column tiles take it.
-    constexpr int TH8 = 16 * MT * (8 / WN) / 16;
-    constexpr int BN = 16 * NT * WN;
-    const long tiles_n = (p0.Npad + BN - 1) / BN;
-    const long blocks8 = (long)((p0.W + 15) / 16) * ((p0.H + TH8 - 1) / TH8) * batch * tiles_n;
-    if (p0.H % TH8 == 0 && blocks8 >= 256 && tiles_n >= 2) return launch3x3_nw<T, MT, NT, WN, 8>(p0, batch, stream);
-  }
-  return launch3x3_nw<T, MT, NT, WN, 4>(p0, batch, stream);
+  return launch3x3_nw<T, MT, NT, WN, 4>(p0, batch, variant, stream);
 }
 
 template <typename T>
@@ -603,6 +626,17 @@ int conv3x3_dispatch(const IgemmParams& p, int batch, int mt, int nt, int wn, hi
   CCVPE_CASE(4, 5, 1) CCVPE_CASE(4, 3, 1) CCVPE_CASE(4, 1, 1) CCVPE_CASE(2, 7, 1)
 #undef CCVPE_CASE
   return fail(CCVPE_EINVAL, "conv3x3: no tile <%d,%d,%d>", mt, nt, wn);
+}
+
+// the form conv3x3_dispatch would launch for this tile (NW | DMA << 4 | TPS << 8), 0 for a tile it does not instantiate; host only
+template <typename T>
+int conv3x3_variant_query(const IgemmParams& p, int batch, int mt, int nt, int wn) {
+#define CCVPE_CASE(MT_, NT_, WN_) \
+  if (mt == MT_ && nt == NT_ && wn == WN_) return conv3x3_variant<T, MT_, NT_, WN_>(p, batch);
+  CCVPE_CASE(4, 5, 2) CCVPE_CASE(4, 4, 2) CCVPE_CASE(4, 3, 2) CCVPE_CASE(4, 2, 2) CCVPE_CASE(4, 1, 2)
+  CCVPE_CASE(4, 5, 1) CCVPE_CASE(4, 3, 1) CCVPE_CASE(4, 1, 1) CCVPE_CASE(2, 7, 1)
+#undef CCVPE_CASE
+  return 0;
 }
 
 }  // namespace ccvpe

@@ -353,7 +353,7 @@ struct MatchFuse { const float* g; int ldg, L, off; float* scores; bool query; }
 
 template <typename T>
 static int conv_igemm_any(const ccvpe_conv_desc* d, void* stream, int out_f32, float* scratch = nullptr,
-                          long* want_floats = nullptr, int* route = nullptr, const MatchFuse* mf = nullptr) {
+                          long* want_floats = nullptr, int* route = nullptr, const MatchFuse* mf = nullptr, int* variant = nullptr) {
   constexpr int E = ElemTraits<T>::E;
   constexpr int SK = 4 * E;
   if (!d) return fail(CCVPE_EINVAL, "conv_igemm: null desc");
@@ -465,6 +465,8 @@ static int conv_igemm_any(const ccvpe_conv_desc* d, void* stream, int out_f32, f
       if (!sk && pw2_supported<T>(p, mt, nt, wn)) fam = CCVPE_ROUTE_PW_RING;
     }
     *route = fam | (mt << 8) | (nt << 12) | (wn << 16);
+    // the form of conv3x3_kernel behind that route (ccvpe_conv3x3_variant): the launcher's own decision, conv3x3_impl.h
+    if (variant) *variant = fam == CCVPE_ROUTE_CONV3X3 ? conv3x3_variant_query<T>(p, d->batch, mt, nt, wn) : 0;
     return CCVPE_OK;
   }
   if (!sk) {
@@ -500,6 +502,12 @@ extern "C" int ccvpe_conv_igemm_route(const ccvpe_conv_desc* d, int is_bf16, int
   const int rc = is_bf16 ? conv_igemm_any<bf16_t>(d, nullptr, out_f32 ? 1 : 0, nullptr, nullptr, &route)
                          : conv_igemm_any<float>(d, nullptr, 1, nullptr, nullptr, &route);
   return rc ? rc : route;
+}
+extern "C" int ccvpe_conv3x3_variant(const ccvpe_conv_desc* d, int is_bf16) {
+  int route = 0, variant = 0;
+  const int rc = is_bf16 ? conv_igemm_any<bf16_t>(d, nullptr, 0, nullptr, nullptr, &route, nullptr, &variant)
+                         : conv_igemm_any<float>(d, nullptr, 1, nullptr, nullptr, &route, nullptr, &variant);
+  return rc ? rc : variant;
 }
 static int match1_offset(int n, int shift, int stride, int window_offset) {
   long o = (-((long)shift * stride + window_offset)) % n;      // match_any()'s offset (csrc/matching.hip)

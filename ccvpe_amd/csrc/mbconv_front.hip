@@ -284,6 +284,13 @@ extern "C" int ccvpe_mbconv_front_route(int in_h, int in_w, int cin, int mid, in
   return (is_bf16 && (g_mbplane_mode & 4) && mbband_takes(in_h, in_w, cin, mid, k, stride, batch)) ? 3 : 2;
 }
 
+// the mbconv_band_kernel<k, stride, nkk, tpw class, ry> instantiation and the chunk grouping ccvpe_mbconv_front_bf16 launches for a
+// shape, or 0 when another kernel (or none) serves it: the same helper the launcher runs (csrc/mbconv_plane.hip: mbband_plan)
+extern "C" int ccvpe_mbconv_band_plan(int in_h, int in_w, int cin, int mid, int k, int stride, int batch) {
+  if (ccvpe_mbconv_front_route(in_h, in_w, cin, mid, k, stride, 1, batch) != 3) return 0;
+  return mbband_plan_packed(in_h, in_w, cin, mid, k, stride, batch);
+}
+
 template <typename TE>
 static int mbconv_front_any(const void* x, const void* w_exp, int kpad, const float* s0, const float* b0,
                             const float* w_dw, const float* s1, const float* b1, void* y, float* se_partial, int B,

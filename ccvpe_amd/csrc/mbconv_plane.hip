@@ -699,11 +699,16 @@ int mbplane_nblk(int H, int W, int cin, int mid, int k, int stride) {
   return g.nbands;
 }
 
-// the band-owner kernel (bf16, fused form): same bands as the geometry above (the squeeze-partial rows must not depend on the
-// kernel), its own CH = 16 row pitch, chunk groups so that the launch is about one workgroup per CU
-static int mbband_launch(const MbpGeom& g, const void* x, const void* w_exp, int kpad, const float* s0, const float* b0,
-                         const float* w_dw, const float* s1, const float* b1, void* y, float* se_partial, int B, int H, int W,
-                         int cin, int mid, int k, int stride, int circular, void* stream) {
+// ---- what the band-owner kernel does with a shape: ONE decision (shape test, row pitch, LDS size, chunk groups), read by the
+// launcher, by mbband_takes (ccvpe_mbconv_front_route) and by ccvpe_mbconv_band_plan — a route can no longer say "band" for a
+// shape the launcher then refuses --------------------------------------------------------------------------------------------
+struct MbBandPlan {
+  int nkk, tpwc, ry;           // the instantiation mbconv_band_kernel<k, stride, nkk, tpwc, ry>
+  int pwp, lds;                // row pitch of the expanded plane in LDS (pixels), dynamic LDS bytes
+  int cpg, ngrp;               // 16-channel slices per workgroup, workgroups per (sample, band)
+};
+
+static bool mbband_plan(const MbpGeom& g, int H, int W, int cin, int mid, int k, int stride, int B, MbBandPlan* out) {
   const int tp = stride == 1 ? k - 1 : k - 2;
   const int Ho = (H + tp - k) / stride + 1, Wo = (W + tp - k) / stride + 1;
   const int nout = stride == 1 ? 4 : 2;
@@ -712,9 +717,10 @@ static int mbband_launch(const MbpGeom& g, const void* x, const void* w_exp, int
   const int rows = IH < H ? IH : H;
   const int ntile = (rows * W + 15) / 16;
   const int tpw = (ntile + 3) / 4;
-  const int nkk = kpad / 32;
-  if (k == 3 && stride == 2) return -1000;
-  if (!((tpw <= 10 && (nkk == 3 || nkk == 4)) || (tpw <= 4 && nkk == 6))) return -1000;
+  const int nkk = (cin + 31) / 32;                   // = kpad / 32 (the entry point checks kpad)
+  if (B <= 0) return false;
+  if (k == 3 && stride == 2) return false;
+  if (!((tpw <= 10 && (nkk == 3 || nkk == 4)) || (tpw <= 4 && nkk == 6))) return false;
   struct PitchKey { int k[5]; int pwp; };
   static thread_local PitchKey pk[16];
   static thread_local int pk_used = 0, pk_next = 0;
@@ -738,26 +744,45 @@ static int mbband_launch(const MbpGeom& g, const void* x, const void* w_exp, int
                          : nkk == 4 ? (k == 3 ? MbBandLds<3, 4>::PARAM_FLOATS : MbBandLds<5, 4>::PARAM_FLOATS)
                                     : (k == 3 ? MbBandLds<3, 6>::PARAM_FLOATS : MbBandLds<5, 6>::PARAM_FLOATS);
   const int lds = (2 * IH * pwp * 20 + param_floats) * 4;
-  if (lds > 160 * 1024) return -1000;
+  if (lds > 160 * 1024) return false;
+  // chunk groups: fewest rounds of (one workgroup per CU) x slices per workgroup
+  const int nchunks = mid / 16;
+  const long base = (long)B * g.nbands;
+  const int cus = num_cus();
+  int best_g = 1;
+  long best_cost = 1L << 60;
+  for (int ng = 1; ng <= nchunks; ++ng) {
+    const int cpg = (nchunks + ng - 1) / ng;
+    const int ngr = (nchunks + cpg - 1) / cpg;
+    const long rounds = (base * ngr + cus - 1) / cus;
+    const long cost = rounds * (cpg + 2);            // + 2: prologue / drain steps of a workgroup
+    if (cost < best_cost) { best_cost = cost; best_g = ngr; }
+  }
+  out->nkk = nkk; out->tpwc = nkk == 6 ? 4 : 10; out->ry = ry; out->pwp = pwp; out->lds = lds;
+  out->cpg = (nchunks + best_g - 1) / best_g;
+  out->ngrp = (nchunks + out->cpg - 1) / out->cpg;
+  return true;
+}
+
+// the band-owner kernel (bf16, fused form): same bands as the geometry above (the squeeze-partial rows must not depend on the
+// kernel), its own CH = 16 row pitch, chunk groups so that the launch is about one workgroup per CU
+static int mbband_launch(const MbpGeom& g, const void* x, const void* w_exp, int kpad, const float* s0, const float* b0,
+                         const float* w_dw, const float* s1, const float* b1, void* y, float* se_partial, int B, int H, int W,
+                         int cin, int mid, int k, int stride, int circular, void* stream) {
+  MbBandPlan pl;
+  if (!mbband_plan(g, H, W, cin, mid, k, stride, B, &pl) || pl.nkk != kpad / 32) return -1000;
+  const int tp = stride == 1 ? k - 1 : k - 2;
+  const int Ho = (H + tp - k) / stride + 1, Wo = (W + tp - k) / stride + 1;
+  const int XG = Wo / (stride == 1 ? 4 : 2);
+  const int nkk = pl.nkk, tpwc = pl.tpwc, ry = pl.ry, pwp = pl.pwp, lds = pl.lds;
   MbBandParams p;
   p.x = reinterpret_cast<const cc_bf16*>(x); p.w_exp = reinterpret_cast<const cc_bf16*>(w_exp);
   p.s0 = s0; p.b0 = b0; p.w_dw = w_dw; p.s1 = s1; p.b1 = b1; p.y = reinterpret_cast<cc_bf16*>(y); p.se_partial = se_partial;
   p.H = H; p.W = W; p.Cin = cin; p.kpad = kpad; p.mid = mid; p.Ho = Ho; p.Wo = Wo; p.circular = circular;
   p.BH = g.BH; p.nbands = g.nbands; p.nchunks = mid / 16; p.PWp = pwp;
-  // chunk groups: fewest rounds of (one workgroup per CU) x slices per workgroup
+  p.cpg = pl.cpg;
+  p.ngrp = pl.ngrp;
   const long base = (long)B * p.nbands;
-  const int cus = num_cus();
-  int best_g = 1;
-  long best_cost = 1L << 60;
-  for (int ng = 1; ng <= p.nchunks; ++ng) {
-    const int cpg = (p.nchunks + ng - 1) / ng;
-    const int ngr = (p.nchunks + cpg - 1) / cpg;
-    const long rounds = (base * ngr + cus - 1) / cus;
-    const long cost = rounds * (cpg + 2);            // + 2: prologue / drain steps of a workgroup
-    if (cost < best_cost) { best_cost = cost; best_g = ngr; }
-  }
-  p.cpg = (p.nchunks + best_g - 1) / best_g;
-  p.ngrp = (p.nchunks + p.cpg - 1) / p.cpg;
   const long total = base * p.ngrp;
   if (total > 0x7fffffffL) return fail(CCVPE_EINVAL, "mbconv_band: grid too large");
   p.total_blocks = (int)total;
@@ -776,7 +801,7 @@ static int mbband_launch(const MbpGeom& g, const void* x, const void* w_exp, int
     hipLaunchKernelGGL(kern, dim3(p.total_blocks), dim3(512), lds, st, p);
     launched = true;
   };
-#define MBB(K_, S_, NKK_, TPW_, RY_) if (k == K_ && stride == S_ && nkk == NKK_ && tpw <= TPW_ && ry == RY_ && !launched && !rc) go(mbconv_band_kernel<K_, S_, NKK_, TPW_, RY_>);
+#define MBB(K_, S_, NKK_, TPW_, RY_) if (k == K_ && stride == S_ && nkk == NKK_ && tpwc == TPW_ && ry == RY_ && !launched && !rc) go(mbconv_band_kernel<K_, S_, NKK_, TPW_, RY_>);
   MBB(3, 1, 3, 10, 2) MBB(5, 1, 3, 10, 2) MBB(3, 1, 4, 10, 2) MBB(5, 1, 4, 10, 2) MBB(5, 2, 3, 10, 2) MBB(5, 2, 4, 10, 2)
   MBB(3, 1, 3, 10, 1) MBB(5, 1, 3, 10, 1) MBB(3, 1, 4, 10, 1) MBB(5, 1, 4, 10, 1) MBB(5, 2, 3, 10, 1) MBB(5, 2, 4, 10, 1)
   MBB(3, 1, 6, 4, 1) MBB(5, 1, 6, 4, 1) MBB(5, 2, 6, 4, 1)
@@ -786,18 +811,16 @@ static int mbband_launch(const MbpGeom& g, const void* x, const void* w_exp, int
   return check_launch("mbconv_band_kernel");
 }
 
-bool mbband_takes(int H, int W, int cin, int mid, int k, int stride, int B) {
+int mbband_plan_packed(int H, int W, int cin, int mid, int k, int stride, int B) {
   MbpGeom g;
-  if (B <= 0 || !mbp_geometry(H, W, mid, k, stride, &g) || mbplane_nblk(H, W, cin, mid, k, stride) <= 0) return false;
-  const int tp = stride == 1 ? k - 1 : k - 2;
-  const int IH = (g.BH - 1) * stride + k;
-  const int rows = IH < H ? IH : H;
-  const int tpw = ((rows * W + 15) / 16 + 3) / 4;
-  const int nkk = (cin + 31) / 32;
-  if (k == 3 && stride == 2) return false;
-  if (!((tpw <= 10 && (nkk == 3 || nkk == 4)) || (tpw <= 4 && nkk == 6))) return false;
-  (void)tp;
-  return true;                                        // (the launcher re-checks the exact LDS size)
+  MbBandPlan pl;
+  if (B <= 0 || !mbp_geometry(H, W, mid, k, stride, &g) || mbplane_nblk(H, W, cin, mid, k, stride) <= 0) return 0;
+  if (!mbband_plan(g, H, W, cin, mid, k, stride, B, &pl)) return 0;
+  return pl.nkk | (pl.tpwc << 4) | (pl.ry << 8) | (pl.cpg << 12) | (pl.ngrp << 20);
+}
+
+bool mbband_takes(int H, int W, int cin, int mid, int k, int stride, int B) {
+  return mbband_plan_packed(H, W, cin, mid, k, stride, B) != 0;
 }
 
 template <typename TE>

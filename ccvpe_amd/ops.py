@@ -85,6 +85,15 @@ def conv_route(desc, is_bf16, out_f32=False):
     return ROUTE_FAMILIES[r & 0xff], (r >> 8) & 0xf, (r >> 12) & 0xf, (r >> 16) & 0xf
 
 
+def conv3x3_variant(desc, is_bf16):
+    """(NW, DMA, TPS) — waves per workgroup, W tile by LDS-DMA, taps per K stage — of the conv3x3_kernel instantiation that serves
+    `desc` (ccvpe_conv3x3_variant: the launcher's own decision), or None when the call does not route to conv3x3_kernel."""
+    r = _lib.load().ccvpe_conv3x3_variant(ctypes.byref(desc), int(bool(is_bf16)))
+    if r < 0:
+        check(int(r), "ccvpe_conv3x3_variant")
+    return (r & 0xf, bool((r >> 4) & 1), (r >> 8) & 0xf) if r else None
+
+
 UPROUTE_KERNELS = {0: "upconv_kernel", 1: "upconv_halo_kernel", 2: "upconv_dma_kernel", 3: "upconv_dma_kernel", 4: "up2_kernel"}
 
 
@@ -153,7 +162,8 @@ def _act_dtype(t):
 
 def conv_igemm(src0, c0, w_packed, n, *, batch, in_h, in_w, kh=1, kw=1, stride=1, pad=0,
                src1=None, c1=0, gate=None, scale=None, shift=None, residual=None, act=ACT_NONE,
-               out_mode=OUT_NHWC, dst=None, ldd=None, ld0=None, ld1=None, algo_k=None, out_f32=False, route_only=False):
+               out_mode=OUT_NHWC, dst=None, ldd=None, ld0=None, ld1=None, algo_k=None, out_f32=False, route_only=False,
+               variant_only=False):
     """Implicit-GEMM conv / deconv / linear (ccvpe_conv_igemm_f32 / _bf16 by src0.dtype).
     src tensors are NHWC.  out_f32 (bf16 only): write an fp32 result."""
     lib = _lib.load()
@@ -191,6 +201,8 @@ def conv_igemm(src0, c0, w_packed, n, *, batch, in_h, in_w, kh=1, kw=1, stride=1
     d.act, d.out_mode = act, out_mode
     if route_only:        # (family, MT, NT, WN) the one-pass entry point would run for this call; nothing is launched
         return conv_route(d, dt != torch.float32, bool(out_f32))
+    if variant_only:      # (NW, DMA, TPS) of conv3x3_kernel for this call, None when another kernel serves it; nothing is launched
+        return conv3x3_variant(d, dt != torch.float32)
     rec = _recorder
     ev0 = rec.begin() if rec is not None else None
     want = lib.ccvpe_conv_igemm_splitk_floats(ctypes.byref(d), int(dt != torch.float32)) if SPLIT_K else 0
@@ -432,6 +444,15 @@ def mbconv_front_supported(in_h, in_w, cin, mid, k, stride):
     if n < 0:
         raise _lib.CcvpeError("ccvpe_mbconv_front_nblk rejected k=%d stride=%d" % (k, stride))
     return n
+
+
+def mbconv_band_plan(in_h, in_w, cin, mid, k, stride, batch):
+    """dict(nkk, tpw, ry, cpg, ngrp) of the mbconv_band_kernel launch the bf16 fused front makes for a shape (ccvpe_mbconv_band_plan:
+    the launcher's own helper), or None when the band kernel does not take it."""
+    r = _lib.load().ccvpe_mbconv_band_plan(in_h, in_w, cin, mid, k, stride, batch)
+    if r <= 0:
+        return None
+    return dict(nkk=r & 0xf, tpw=(r >> 4) & 0xf, ry=(r >> 8) & 0xf, cpg=(r >> 12) & 0xff, ngrp=(r >> 20) & 0xff)
 
 
 def mbconv_front(x, w_exp, s0, b0, w_dw, s1, b1, mid, k, stride, circular):

@@ -104,6 +104,11 @@ int ccvpe_conv_igemm_splitk_floats(const ccvpe_conv_desc* desc, int is_bf16);
 #define CCVPE_ROUTE_PW_RING 4 /* pointwise kernel with a three-stage LDS-DMA ring, two workgroups per CU, fp32 and bf16 (csrc/conv_pw2_impl.h) */
 #define CCVPE_ROUTE_PWN 5     /* (ABI 7) narrow projection kernel: N <= 48, K <= 256 (fp32: <= 144), weights x SE gate in registers, waves stream 16-pixel tiles (csrc/pwn.hip); the route's MT / NT fields hold N / 16 and K bytes / 64 */
 int ccvpe_conv_igemm_route(const ccvpe_conv_desc* desc, int is_bf16, int out_f32);
+/* Which form of the 3x3 kernel runs for a `desc` that routes to CCVPE_ROUTE_CONV3X3 (storage output, no out_f32):
+ * NW | DMA << 4 | TPS << 8 — waves per workgroup (4 or 8: the 8-wave form doubles the pixel tile), W tile by LDS-DMA (1) or
+ * through registers (0), taps per K stage (3 = a row of taps, 1).  0 for any other route, negative = error.  Host only: the
+ * launcher's own decision (csrc/conv3x3_impl.h: conv3x3_variant), so that a test can assert the form before it launches. */
+int ccvpe_conv3x3_variant(const ccvpe_conv_desc* desc, int is_bf16);
 /* A/B switch for measurements (process-wide, default on): 0 sends the narrow bf16 decoder layers (CCVPE_ROUTE_C3N, and the
  * narrow form of ccvpe_upconv3x3_bf16) back to the tiled kernels.  Returns the previous setting. */
 int ccvpe_set_narrow_kernels(int on);
@@ -282,6 +287,12 @@ int ccvpe_mbconv_front_nblk(int in_h, int in_w, int cin, int mid, int k, int str
 /* (ABI 7) which kernel the fused call runs for a shape — 0 none (use the unfused calls), 1 mbconv_front_kernel (early blocks),
  * 2 mbconv_plane_kernel, 3 mbconv_band_kernel (late blocks: planes of <= 1024 pixels; 3 = bf16 storage only).  Reporting only. */
 int ccvpe_mbconv_front_route(int in_h, int in_w, int cin, int mid, int k, int stride, int is_bf16, int batch);
+/* The mbconv_band_kernel<k, stride, nkk, tpw, ry> instantiation and the chunk grouping that ccvpe_mbconv_front_bf16 launches
+ * for a shape: nkk | tpw << 4 | ry << 8 | cpg << 12 | ngrp << 20 (nkk = 32-channel K pieces of the expand conv, tpw = the
+ * 10- or 4-tile class, ry = output rows per depthwise thread, cpg = 16-channel slices per workgroup, ngrp = workgroups per
+ * sample and band; cpg depends on the device's CU count and on batch), or 0 when route != 3.  Host only; the launcher,
+ * ccvpe_mbconv_front_route and this query share one helper (csrc/mbconv_plane.hip: mbband_plan). */
+int ccvpe_mbconv_band_plan(int in_h, int in_w, int cin, int mid, int k, int stride, int batch);
 int ccvpe_mbconv_front_f32(const float* x, const float* w_exp, int kpad, const float* s0, const float* b0,
                            const float* w_dw, const float* s1, const float* b1, float* y, float* se_partial,
                            int batch, int in_h, int in_w, int cin, int mid, int k, int stride, int circular,

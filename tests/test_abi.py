@@ -279,3 +279,113 @@ def test_fullsize_train_kernel_table_matches_the_geometry_queries():
     assert any(row[-1] == 48 for row in S.MATCH_BWD) and any(row[-2] == 32 for row in S.MATCH_BWD)   # NPAD 48, 32 slices
     for name, rows, c, ld in S.COLSUM:
         assert rows >= S.CS_ROWS * 256, "%s: not the many-rows branch" % name
+
+
+def _conv3x3_desc(row, bf16):
+    """descriptor of a tests/forward_kernel_shapes.py ConvRow (fake aligned pointers: the queries never dereference them)"""
+    sk = 32 if bf16 else 16
+    d = _lib.ConvDesc()
+    d.src0 = d.src1 = d.w = d.dst = d.shift = 256
+    d.c0, d.ld0, d.c1, d.ld1 = row.c0, row.ld0, row.c1, row.c1
+    d.batch, d.in_h, d.in_w = row.b, row.h, row.w
+    d.kh = d.kw = 3
+    d.stride, d.pad, d.act = 1, 1, 1
+    d.n, d.ldd = row.n, row.n
+    d.kpad = (9 * (row.c0 + row.c1) + sk - 1) // sk * sk
+    return d
+
+
+def test_forward_kernel_table_matches_the_conv3x3_queries():
+    """Host-only: every conv3x3 row of tests/forward_kernel_shapes.py routes to conv3x3_kernel with the tile and the form
+    (waves, W by LDS-DMA, taps per stage) it is there for, un-split; NW flips between the two members of every threshold pair; and
+    the rows reach every instantiation the traced B = 64 steps launch (the literal lists in the table file)."""
+    import ctypes
+    import forward_kernel_shapes as S
+    lib = _lib.load()
+    seen = {0: set(), 1: set()}
+    for row in S.conv_rows():
+        for bf16, want in ((0, row.f32), (1, row.bf16)):
+            if want is None:
+                continue
+            d = _conv3x3_desc(row, bf16)
+            r = lib.ccvpe_conv_igemm_route(ctypes.byref(d), bf16, 0)
+            assert r & 0xff == 2, "%s (%s): route family %d, not conv3x3_kernel" % (row.name, "bf16" if bf16 else "fp32", r & 0xff)
+            assert ((r >> 8) & 0xf, (r >> 12) & 0xf, (r >> 16) & 0xf) == row.tile, row.name
+            v = lib.ccvpe_conv3x3_variant(ctypes.byref(d), bf16)
+            assert (v & 0xf, bool((v >> 4) & 1), v >> 8) == want, "%s (%s): variant %#x" % (row.name, "bf16" if bf16 else "fp32", v)
+            assert lib.ccvpe_conv_igemm_splitk_floats(ctypes.byref(d), bf16) == 0, "%s: would run split-K (generic kernel)" % row.name
+            if bf16:
+                assert lib.ccvpe_conv_igemm_route(ctypes.byref(d), 1, 1) == r, "%s: out_f32 changes the route" % row.name
+            seen[bf16].add(row.tile + want)
+    for hi, lo in S.CONV3X3_NW8_PAIRS:
+        assert (hi.b - lo.b, hi.h, hi.w, hi.n, hi.tile) == (1, lo.h, lo.w, lo.n, lo.tile), hi.name
+        for a, b in ((hi.f32, lo.f32), (hi.bf16, lo.bf16)):
+            assert (a is None) == (b is None) and (a is None or (a[0], b[0]) == (8, 4)), "%s: NW does not flip 8 -> 4" % hi.name
+    assert set(S.CONV3X3_TRACED_F32) <= seen[0], sorted(set(S.CONV3X3_TRACED_F32) - seen[0])
+    assert set(S.CONV3X3_TRACED_BF16) <= seen[1], sorted(set(S.CONV3X3_TRACED_BF16) - seen[1])
+    # not a conv3x3_kernel route -> 0: a 1x1 layer, and a single-source bf16 layer the narrow kernel takes when the plane is large
+    d = _conv3x3_desc(S.CONV3X3[0], 0)
+    d.kh = d.kw = 1
+    d.pad, d.kpad = 0, 48
+    assert lib.ccvpe_conv3x3_variant(ctypes.byref(d), 0) == 0
+    assert lib.ccvpe_conv3x3_variant(None, 0) == -1
+
+
+def test_conv3x3_w_tile_is_always_staged_by_lds_dma():
+    """pick_cfg (csrc/conv_common.h) charges a tile by the columns it computes, and the 16-wide tile computes exactly Npad: the
+    cheapest tile always divides Npad, so launch3x3_nw's `Npad % BN != 0` branch — conv3x3_kernel<.., DMA = false, 1>, W through
+    registers — is unreachable through ccvpe_conv_igemm_* (DESIGN.md section 4).  Every N the ABI accepts up to twice the model's
+    widest layer, both types, a small and a B = 64 launch."""
+    import ctypes
+    import forward_kernel_shapes as S
+    lib = _lib.load()
+    for bf16 in (0, 1):
+        for b, h, w in ((2, 11, 20), (64, 64, 64)):
+            d = _conv3x3_desc(S.CONV3X3[0]._replace(b=b, h=h, w=w), bf16)
+            for n in range(8, 1297):
+                d.n, d.ldd = n, (n + 7) // 8 * 8
+                v = lib.ccvpe_conv3x3_variant(ctypes.byref(d), bf16)
+                assert v > 0 and (v >> 4) & 1 == 1, "N = %d (%s): variant %#x" % (n, "bf16" if bf16 else "fp32", v)
+
+
+def test_forward_kernel_table_matches_the_band_plan_query():
+    """Host-only: every band row of tests/forward_kernel_shapes.py is taken by mbconv_band_kernel with the instantiation it is
+    there for and — num_cus() falls back to 256 without a GPU, the MI355X's count — the slices per workgroup, the groups and the
+    short last group the row's comment promises; the rows reach every traced instantiation; the slice-per-workgroup switch turns
+    the plan off; and a shape the launcher refuses for its LDS need is no longer reported as "band"."""
+    import torch
+    import forward_kernel_shapes as S
+    lib = _lib.load()
+    if torch.cuda.is_available() and torch.cuda.get_device_properties(0).multi_processor_count != 256:
+        pytest.skip("the table stores the grouping for 256 CUs")     # (never on the MI355X or on a box without a GPU)
+    seen = set()
+    for row in S.BAND:
+        mid = 6 * row.cin
+        assert lib.ccvpe_mbconv_front_route(row.h, row.w, row.cin, mid, row.k, row.s, 1, row.b) == 3, row.name
+        assert lib.ccvpe_mbconv_front_route(row.h, row.w, row.cin, mid, row.k, row.s, 0, row.b) == 2, row.name     # fp32: plane kernel
+        p = lib.ccvpe_mbconv_band_plan(row.h, row.w, row.cin, mid, row.k, row.s, row.b)
+        assert p > 0, row.name
+        nkk, tpw, ry, cpg, ngrp = p & 0xf, (p >> 4) & 0xf, (p >> 8) & 0xf, (p >> 12) & 0xff, (p >> 20) & 0xff
+        assert (row.k, row.s, nkk, tpw, ry) == row.inst, "%s: instantiation <%d,%d,%d,%d,%d>" % (row.name, row.k, row.s, nkk, tpw, ry)
+        assert (cpg, ngrp) == (row.cpg256, row.ngrp256), "%s: cpg %d ngrp %d" % (row.name, cpg, ngrp)
+        assert mid // 16 - (ngrp - 1) * cpg == row.last and 0 < row.last <= cpg, row.name
+        assert row.deep == (cpg >= 3), row.name
+        assert max(row.b * row.h * row.w * row.cin, row.b * row.h * row.w * mid // row.s ** 2) * 2 < 64 << 20, "%s: a tensor above 64 MB" % row.name
+        seen.add(row.inst)
+    assert set(S.BAND_TRACED) <= seen, sorted(set(S.BAND_TRACED) - seen)
+    assert any(r.deep and r.last < r.cpg256 for r in S.BAND) and any(r.cpg256 >= 18 for r in S.BAND)
+    row = S.BAND[3]
+    prev = lib.ccvpe_set_mbconv_plane_kernels(3)
+    try:
+        assert lib.ccvpe_mbconv_front_route(row.h, row.w, row.cin, 6 * row.cin, row.k, row.s, 1, row.b) == 2
+        assert lib.ccvpe_mbconv_band_plan(row.h, row.w, row.cin, 6 * row.cin, row.k, row.s, row.b) == 0
+    finally:
+        lib.ccvpe_set_mbconv_plane_kernels(prev)
+    h, w, cin, k, s = S.BAND_LDS_REFUSED
+    assert lib.ccvpe_mbconv_front_nblk(h, w, cin, 6 * cin, k, s) == 1                # the plane geometry takes it: one band of 9 rows
+    ih, tiles = (h - 1) * s + k, (min((h - 1) * s + k, h) * w + 15) // 16            # 13 plane rows; 32 tiles = 8 per wave <= 10, 4 K pieces
+    assert (tiles + 3) // 4 <= 10 and (cin + 31) // 32 == 4
+    assert 2 * ih * (w + k - 1) * 20 * 4 > 120 * 1024                                 # the two planes alone, before the pitch padding
+    assert lib.ccvpe_mbconv_front_route(h, w, cin, 6 * cin, k, s, 1, 3) == 2, "route says band for a shape the launcher refuses"
+    assert lib.ccvpe_mbconv_band_plan(h, w, cin, 6 * cin, k, s, 3) == 0
+    assert lib.ccvpe_mbconv_band_plan(16, 16, 192, 1152, 5, 1, 0) == 0               # no batch

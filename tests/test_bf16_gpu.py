@@ -91,6 +91,10 @@ def test_mbconv_plane_late_blocks_bf16(ops, k, s, cin, h, w, circ):
     want = O.swish(O.same_conv(t, w_dw, k, s, 224, circ, groups=mid) * s1.view(1, -1, 1, 1) + b1.view(1, -1, 1, 1))
     f32 = torch.float32
     assert ops.mbconv_front_supported(h, w, cin, mid, k, s) > 0
+    from ccvpe_amd import _lib
+    lib = _lib.load()
+    assert lib.ccvpe_mbconv_front_route(h, w, cin, mid, k, s, 1, b) == 3, "the default is not the band-owner kernel for this row"
+    assert ops.mbconv_band_plan(h, w, cin, mid, k, s, b) is not None
     wd = dev(w_dw.reshape(mid, k, k).permute(1, 2, 0), f32)
     got, part = ops.mbconv_front(dev(nhwc(x)), dev(pack(w_exp)), dev(s0, f32), dev(b0, f32), wd, dev(s1, f32), dev(b1, f32),
                                  mid, k, s, circ)
@@ -99,10 +103,10 @@ def test_mbconv_plane_late_blocks_bf16(ops, k, s, cin, h, w, circ):
     close(part.sum(1), want.sum(dim=(2, 3)), 2e-3, "squeeze partials (fp32 sums of unrounded outputs)")
     # the default above is the band-owner kernel (producer / consumer waves); the slice-per-workgroup kernel behind the same entry
     # point must agree with it to the last bf16 bit or two (same arithmetic, another summation order inside the MFMA chain)
-    from ccvpe_amd import _lib
-    lib = _lib.load()
     prev = lib.ccvpe_set_mbconv_plane_kernels(3)
     try:
+        assert lib.ccvpe_mbconv_front_route(h, w, cin, mid, k, s, 1, b) == 2, "mode 3 must be the slice-per-workgroup kernel"
+        assert ops.mbconv_band_plan(h, w, cin, mid, k, s, b) is None
         got1, part1 = ops.mbconv_front(dev(nhwc(x)), dev(pack(w_exp)), dev(s0, f32), dev(b0, f32), wd, dev(s1, f32), dev(b1, f32),
                                        mid, k, s, circ)
     finally:

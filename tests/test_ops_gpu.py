@@ -259,6 +259,20 @@ def test_igemm_deconv_pixel_shuffle(ops, cin, cout, hw):
     close(nchw(got), want, 1e-4, "deconv")
 
 
+# (cp, h1, w1, bf16) of the w1 >= 16 rows below -> (kernel, MT, NT, WN) their comments name: fp32 on the low-res-halo kernel, bf16 on
+# the LDS-DMA kernel unless its W-row precondition fails (cp = 48, 88)
+UPCONV_TILED_ROUTES = {
+    (48, 17, 33, False): ("upconv_halo_kernel", 4, 1, 1), (88, 18, 16, False): ("upconv_halo_kernel", 4, 3, 1),
+    (168, 9, 20, False): ("upconv_halo_kernel", 4, 5, 1), (328, 7, 17, False): ("upconv_halo_kernel", 4, 5, 2),
+    (648, 5, 16, False): ("upconv_halo_kernel", 4, 5, 2), (64, 19, 35, False): ("upconv_halo_kernel", 4, 1, 2),
+    (128, 8, 32, False): ("upconv_halo_kernel", 4, 2, 2), (256, 6, 16, False): ("upconv_halo_kernel", 4, 4, 2),
+    (88, 18, 16, True): ("upconv_halo_kernel", 4, 3, 1), (48, 17, 33, True): ("upconv_halo_kernel", 4, 1, 1),
+    (168, 9, 20, True): ("upconv_dma_kernel", 4, 5, 1), (648, 5, 16, True): ("upconv_dma_kernel", 4, 5, 2),
+    (64, 19, 35, True): ("upconv_dma_kernel", 4, 1, 2), (328, 7, 17, True): ("upconv_dma_kernel", 4, 5, 2),
+    (256, 6, 16, True): ("upconv_dma_kernel", 4, 4, 2),
+}
+
+
 @pytest.mark.parametrize("cp,cref,cd,c1,co,h1,w1,bf16", [
     (48, 41, 16, 0, 16, 9, 11, False),        # level 1 (no skip)
     (88, 81, 40, 16, 40, 6, 7, False),        # level 2
@@ -292,7 +306,8 @@ def test_igemm_deconv_pixel_shuffle(ops, cin, cout, hw):
     (136, 129, 32, 16, 32, 64, 512, True),
 ])
 def test_upconv_folds_deconv_into_conv3x3(ops, cp, cref, cd, c1, co, h1, w1, bf16):
-    """relu(conv3x3(cat[deconv2x2s2(x)+b, skip])+b)  ==  the folded per-parity GEMM (incl. borders)."""
+    """relu(conv3x3(cat[deconv2x2s2(x)+b, skip])+b)  ==  the folded per-parity GEMM (incl. borders).  The kernel (and tile) each row's
+    comment names is asserted through ccvpe_upconv3x3_route before the launch."""
     from ccvpe_amd.models import _pack_upconv
     b = 2
     dt = torch.bfloat16 if bf16 else torch.float32
@@ -308,6 +323,13 @@ def test_upconv_folds_deconv_into_conv3x3(ops, cp, cref, cd, c1, co, h1, w1, bf1
     want = F.relu(F.conv2d(torch.cat([d, skip], 1) if c1 else d, w3, b3, padding=1))
     fw, fshift = _pack_upconv(wd.cuda(), bd.cuda(), [(0, 0, cref)], cp, w3.cuda(), b3.cuda(), dt)
     xd, sk = nhwc(x).to(dt).cuda().contiguous(), (nhwc(skip).to(dt).cuda().contiguous() if c1 else None)
+    route = ops.upconv3x3(xd, cp, fw, fshift, co, batch=b, h1=h1, w1=w1, src1=sk, c1=c1, act=ops.ACT_RELU, route_only=True)
+    if h1 * w1 >= 128 * 256:
+        assert route[0] == "up2_kernel", route
+    elif w1 < 16:                                           # images narrower than a halo tile: the gather kernel
+        assert route[0] == "upconv_kernel" and not route[4], route
+    else:
+        assert route == UPCONV_TILED_ROUTES[(cp, h1, w1, bf16)] + (False,), route
     got = ops.upconv3x3(xd, cp, fw, fshift, co, batch=b, h1=h1, w1=w1, src1=sk, c1=c1, act=ops.ACT_RELU)
     close(nchw(got).float(), want, 2e-2 if bf16 else 1e-4, "upconv cp=%d" % cp)
     if h1 * w1 >= 128 * 256:                                # the narrow-level kernel must be the one that ran, and agree with the tiled one
@@ -341,8 +363,10 @@ def test_upconv_level6_packs_two_images_per_tile(ops, b, bf16):
     d = F.conv_transpose2d(x[:, :cref], wd, bd, stride=2)
     want = F.relu(F.conv2d(torch.cat([d, skip], 1), w3, b3, padding=1))
     fw, fshift = _pack_upconv(wd.cuda(), bd.cuda(), [(0, 0, cref)], cp, w3.cuda(), b3.cuda(), dt)
-    got = ops.upconv3x3(nhwc(x).to(dt).cuda().contiguous(), cp, fw, fshift, co, batch=b, h1=h1, w1=w1,
-                        src1=nhwc(skip).to(dt).cuda().contiguous(), c1=c1, act=ops.ACT_RELU)
+    xd, sk = nhwc(x).to(dt).cuda().contiguous(), nhwc(skip).to(dt).cuda().contiguous()
+    route = ops.upconv3x3(xd, cp, fw, fshift, co, batch=b, h1=h1, w1=w1, src1=sk, c1=c1, act=ops.ACT_RELU, route_only=True)
+    assert route == ("upconv_dma_kernel", 4, 5, 2, True), "not the PAIR form of upconv_dma_kernel: %s" % (route,)
+    got = ops.upconv3x3(xd, cp, fw, fshift, co, batch=b, h1=h1, w1=w1, src1=sk, c1=c1, act=ops.ACT_RELU)
     for i in range(b):
         close(nchw(got).float()[i], want[i], 2e-2 if bf16 else 1e-4, "level-6 pair, image %d" % i)
 
