@@ -93,6 +93,8 @@ PROTOTYPES = {
     "ccvpe_upconv3x3_f32": (c_int, [ctypes.POINTER(UpconvDesc), c_void_p]),
     "ccvpe_upconv3x3_bf16": (c_int, [ctypes.POINTER(UpconvDesc), c_void_p]),
     "ccvpe_upconv3x3_route": (c_int, [ctypes.POINTER(UpconvDesc), c_int]),
+    "ccvpe_upconv3x3_s3_ok": (c_int, [ctypes.POINTER(UpconvDesc)]),
+    "ccvpe_upconv3x3_s3_f32": (c_int, [ctypes.POINTER(UpconvDesc), c_void_p]),
     "ccvpe_stem_conv_f32": (c_int, [c_void_p] * 5 + [c_int] * 4 + [c_void_p]),
     "ccvpe_dwconv_nblk": (c_int, [c_int] * 4),
     "ccvpe_dwconv_f32": (c_int, [c_void_p] * 6 + [c_int] * 7 + [c_void_p]),

@@ -187,6 +187,10 @@ FUSE_TAIL = __import__("os").environ.get("CCVPE_FUSE_TAIL", "1") != "0"
 SPLIT_TAIL = __import__("os").environ.get("CCVPE_SPLIT_TAIL", "1") != "0"
 # fp32 convK.2 layers by Winograd F(2x2,3x3) where the library serves the shape (csrc/conv3x3_wino.hip); CCVPE_WINO=0 = direct (A/B runs)
 WINO = __import__("os").environ.get("CCVPE_WINO", "1") != "0"
+# fp32 folded deconv + conv.0 layers on the bf16 matrix cores with three bf16 planes per operand where the library's size rule prefers
+# it (csrc/upconv_s3.hip); CCVPE_SPLIT3=0 = the fp32 kernels (A/B runs)
+SPLIT3 = __import__("os").environ.get("CCVPE_SPLIT3", "1") != "0"
+SPLIT3_MIN_OK = 2          # ccvpe_upconv3x3_s3_ok value a layer needs for the route (tests open the size rule with 1)
 # train mode: replay the per-step weight re-pack as one hipGraph (see _CVMBase._packed); CCVPE_PACK_GRAPH=0 keeps it eager
 PACK_GRAPH = __import__("os").environ.get("CCVPE_PACK_GRAPH", "1") != "0"
 # train mode, fp32: the per-step re-pack as ONE gather launch (ccvpe_amd/repack.py); CCVPE_PACK_GATHER=0 keeps the graph replay
@@ -237,6 +241,38 @@ def _pack_upconv(wd, bd, col_map, cp, w3, b3, dtype=torch.float32):
                     v += w3d[:, :, ky, kx] @ bd.double()
             shift9[rc * 3 + cc] = v
     return out.to(dtype).contiguous(), shift9.float().contiguous()
+
+
+def _split3_bf16(v):
+    """fp32 tensor -> (hi, mid, lo) bf16 planes, round-to-nearest: hi = bf16(v), mid = bf16(v - hi), lo = bf16(v - hi - mid).
+    Both subtractions are exact in fp32 and hi + mid + lo == v exactly (8 + 8 + 8 significant bits) for finite v whose planes
+    stay normal; csrc/upconv_s3.hip splits the activations the same way in registers."""
+    hi = v.to(torch.bfloat16)
+    r = v - hi.float()
+    mid = r.to(torch.bfloat16)
+    lo = (r - mid.float()).to(torch.bfloat16)
+    return hi, mid, lo
+
+
+def _pack_upconv_s3(fw, cp, c1, dtype=torch.float32):
+    """The fp32 pack of _pack_upconv -> the three-bf16-plane pack of ccvpe_upconv3x3_s3_f32 (csrc/upconv_s3.hip).
+
+    Every fp32 weight v is split round-to-nearest into hi = bf16(v), mid = bf16(v - hi), lo = bf16(v - hi - mid); both
+    subtractions are exact and hi + mid + lo == v exactly, so both routes multiply by the same effective weights.
+    Layout [4 parities][stage][Co^16][hi 16 | mid 16 | lo 16] in the kernel's stage order: each of the 4 low-res taps and
+    of the 9 skip taps is zero-padded to 16-channel blocks; stage = block * 4 + tap for the low-res source, then
+    4 * ceil(cp / 16) + tap * ceil(c1 / 16) + block for the skip.  None for anything but an fp32 pack with a skip."""
+    if dtype != torch.float32 or fw is None or fw.dtype != torch.float32 or c1 <= 0:
+        return None
+    npad = fw.shape[1]
+    nb0, nb1 = (cp + 15) // 16, (c1 + 15) // 16
+    a = fw.new_zeros((4, npad, 4, nb0 * 16))
+    a[..., :cp] = fw[:, :, :4 * cp].reshape(4, npad, 4, cp)
+    a = a.reshape(4, npad, 4, nb0, 16).permute(0, 3, 2, 1, 4).reshape(4, 4 * nb0, npad, 16)
+    s = fw.new_zeros((4, npad, 9, nb1 * 16))
+    s[..., :c1] = fw[:, :, 4 * cp:4 * cp + 9 * c1].reshape(4, npad, 9, c1)
+    s = s.reshape(4, npad, 9, nb1, 16).permute(0, 2, 3, 1, 4).reshape(4, 9 * nb1, npad, 16)
+    return torch.cat(_split3_bf16(torch.cat([a, s], 1)), -1).contiguous()
 
 
 def _pack_backward(sd, kind, pk):
@@ -341,6 +377,7 @@ def _pack_model(sd, kind, n_tail, dtype=torch.float32, fold=True, f32_tail=0):
             lv.fw, lv.fshift = _pack_upconv(sd["deconv%d.weight" % lvl], sd["deconv%d.bias" % lvl],
                                             [(0, 1, c), (c, 0, 1)], ldo, sd["conv%d.0.weight" % lvl],
                                             sd["conv%d.0.bias" % lvl], dtype)
+            lv.fw3 = _pack_upconv_s3(lv.fw, ldo, lv.c1, dtype if base_dtype == torch.float32 else None)
         lv.w_a = _pack_conv(sd["conv%d.0.weight" % lvl], dtype)
         lv.b_a = sd["conv%d.0.bias" % lvl].contiguous()
         if lvl != 1:
@@ -373,6 +410,7 @@ def _pack_model(sd, kind, n_tail, dtype=torch.float32, fold=True, f32_tail=0):
             ov.fw, ov.fshift = _pack_upconv(sd["deconv%d_ori.weight" % lvl], sd["deconv%d_ori.bias" % lvl], cmap,
                                             ov.k, sd["conv%d_ori.0.weight" % lvl], sd["conv%d_ori.0.bias" % lvl],
                                             dtype)
+            ov.fw3 = _pack_upconv_s3(ov.fw, ov.k, ov.c1, dtype)
         ov.w_a = _pack_conv(sd["conv%d_ori.0.weight" % lvl], dtype)
         ov.b_a = sd["conv%d_ori.0.bias" % lvl].contiguous()
         ov.n_a = c_out
@@ -444,6 +482,16 @@ def _conv_b(lv, y, batch, hw, out_f32=False):
         return ops.conv3x3_wino(y, lv.n_a, lv.u_b, lv.n_b, batch=batch, in_h=hw, in_w=hw, shift=lv.b_b)
     return ops.conv_igemm(y, lv.n_a, lv.w_b, lv.n_b, batch=batch, in_h=hw, in_w=hw, kh=3, kw=3, pad=1, shift=lv.b_b,
                           out_f32=out_f32)
+
+
+def _upconv_a(lv, x, k, batch, hw, skip):
+    """deconv folded into conv.0 (+ ReLU), one GEMM per output parity: the three-plane bf16 kernel where the pack exists (eval,
+    fp32) and the library's size rule prefers it, else ccvpe_upconv3x3."""
+    fw3 = getattr(lv, "fw3", None)
+    if (SPLIT3 and fw3 is not None and
+            ops.upconv3x3_s3_ok(x, k, fw3, lv.n_a, batch=batch, h1=hw, w1=hw, src1=skip, c1=lv.c1) >= SPLIT3_MIN_OK):
+        return ops.upconv3x3_s3(x, k, fw3, lv.fshift, lv.n_a, batch=batch, h1=hw, w1=hw, src1=skip, c1=lv.c1, act=ops.ACT_RELU)
+    return ops.upconv3x3(x, k, lv.fw, lv.fshift, lv.n_a, batch=batch, h1=hw, w1=hw, src1=skip, c1=lv.c1, act=ops.ACT_RELU)
 
 
 class _CVMBase(nn.Module):
@@ -603,8 +651,7 @@ class _CVMBase(nn.Module):
                 # the whole 512 x 512 level in one launch: deconv1_ori + conv1_ori + F.normalize (models.py:145-148,341)
                 return ops.tail512(xo, ov.k, ov.fw, ov.fshift, ov.w_b, ov.b_b, 2, normalize, batch=batch, h1=hw, w1=hw)
             if j in FOLD_LEVELS and batch * hw * hw >= FOLD_MIN_PIXELS:
-                y = ops.upconv3x3(xo, ov.k, ov.fw, ov.fshift, ov.n_a, batch=batch, h1=hw, w1=hw,
-                                  src1=skip, c1=ov.c1, act=ops.ACT_RELU)
+                y = _upconv_a(ov, xo, ov.k, batch, hw, skip)
             else:
                 up = ops.conv_igemm(xo, ov.k, ov.up_w, ov.up_n, batch=batch, in_h=hw, in_w=hw,
                                     shift=ov.up_b, out_mode=ops.OUT_DECONV2X, algo_k=ov.k_algo)
@@ -743,8 +790,7 @@ class _CVMBase(nn.Module):
                                                   want_softmax=True)
                     break
                 if j in FOLD_LEVELS and batch * hw * hw >= FOLD_MIN_PIXELS:   # deconv folded into conv.0: one GEMM per output parity
-                    y = ops.upconv3x3(cat, lv.ldo, lv.fw, lv.fshift, lv.n_a, batch=batch, h1=hw, w1=hw,
-                                      src1=skip, c1=lv.c1, act=ops.ACT_RELU)
+                    y = _upconv_a(lv, cat, lv.ldo, batch, hw, skip)
                 else:
                     up = ops.conv_igemm(cat, lv.ldo, lv.up_w, lv.up_n, batch=batch, in_h=hw, in_w=hw,
                                         shift=lv.up_b, out_mode=ops.OUT_DECONV2X, algo_k=lv.c + 1)

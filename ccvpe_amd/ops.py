@@ -317,6 +317,61 @@ def upconv3x3(src0, c0, w_packed, shift9, n, *, batch, h1, w1, src1=None, c1=0, 
     return dst
 
 
+def _s3_desc(src0, c0, w3_packed, shift9, n, batch, h1, w1, src1, c1, act, dst, ldd, ld0, ld1):
+    d = _lib.UpconvDesc()
+    d.src0, d.src1, d.w, d.shift9 = _ptr(src0), _ptr(src1), _ptr(w3_packed), _ptr(shift9)
+    d.dst = _ptr(dst) if dst is not None else None
+    d.c0, d.ld0, d.c1, d.ld1 = c0, ld0, c1, ld1
+    d.batch, d.h1, d.w1 = batch, h1, w1
+    d.n, d.kpad, d.ldd, d.act = n, w3_packed.shape[1] * w3_packed.shape[3], ldd, act
+    return d
+
+
+def upconv3x3_s3_ok(src0, c0, w3_packed, n, *, batch, h1, w1, src1=None, c1=0, ldd=None, ld0=None, ld1=None):
+    """ccvpe_upconv3x3_s3_ok for this layer: 0 = not served (also: anything but fp32 tensors, no three-plane pack), 1 = the
+    kernel computes it, 2 = and the library's measured size rule prefers it to ccvpe_upconv3x3_f32.  Nothing is launched."""
+    if w3_packed is None or src0.dtype != torch.float32 or (src1 is not None and src1.dtype != torch.float32):
+        return 0
+    if w3_packed.dtype != torch.bfloat16 or w3_packed.dim() != 4:
+        return 0
+    ld0 = ld0 if ld0 is not None else src0.shape[-1]
+    ld1 = ld1 if ld1 is not None else (src1.shape[-1] if src1 is not None else 0)
+    d = _s3_desc(src0, c0, w3_packed, None, n, batch, h1, w1, src1, c1, ACT_NONE, None, ldd if ldd is not None else n, ld0, ld1)
+    return int(_lib.load().ccvpe_upconv3x3_s3_ok(ctypes.byref(d)))
+
+
+def upconv3x3_s3(src0, c0, w3_packed, shift9, n, *, batch, h1, w1, src1=None, c1=0, act=ACT_NONE, dst=None, ldd=None, ld0=None,
+                 ld1=None):
+    """ccvpe_upconv3x3_f32's layer with its products on the bf16 matrix cores, three bf16 planes per fp32 operand
+    (ccvpe_upconv3x3_s3_f32); w3_packed from models._pack_upconv_s3.  Same result as upconv3x3 to fp32 rounding, not bit for
+    bit.  fp32 tensors only; a layer the kernel does not serve is an error (no fallback)."""
+    lib = _lib.load()
+    for t, nm in ((src0, "src0"), (src1, "src1"), (shift9, "shift9"), (dst, "dst")):
+        _chk(t, nm)
+    _chk(w3_packed, "w", torch.bfloat16)
+    ld0 = ld0 if ld0 is not None else src0.shape[-1]
+    ld1 = ld1 if ld1 is not None else (src1.shape[-1] if src1 is not None else 0)
+    if dst is None:
+        ldd = ldd if ldd is not None else n
+        dst = _empty((batch, 2 * h1, 2 * w1, ldd), device=src0.device)
+    elif ldd is None:
+        ldd = dst.shape[-1]
+    d = _s3_desc(src0, c0, w3_packed, shift9, n, batch, h1, w1, src1, c1, act, dst, ldd, ld0, ld1)
+    rec = _recorder
+    ev0 = rec.begin() if rec is not None else None
+    check(lib.ccvpe_upconv3x3_s3_f32(ctypes.byref(d), _stream()), "ccvpe_upconv3x3_s3_f32")
+    if rec is not None:
+        # the fp32 layer's FLOPs and bytes (as upconv3x3): this kernel's "TF" in the bench tables can exceed the fp32 peak
+        m = batch * h1 * w1 * 4
+        k_eff = 4 * c0 + 9 * c1
+        flops = 2.0 * m * n * k_eff
+        nbytes = 4.0 * (batch * h1 * w1 * c0 + m * c1 + m * n + 4 * n * k_eff)
+        tile = igemm_tile(n).split("<")[1]
+        name = "upconv_s3_kernel<%s%s" % (tile[:-1], ",pair>" if (h1 == 8 and w1 == 8) else ">")
+        rec.end(name, "up3x3 M%d N%d Keff%d" % (m, n, k_eff), flops, nbytes, ev0)
+    return dst
+
+
 def tail512(x, c0, w_packed, shift9, w2, b2, cout, normalize, *, batch, h1, w1, split=False, want_softmax=False):
     """The whole 512 x 512 decoder level in one launch (ccvpe_tail512_f32 / _bf16): folded deconv + conv.0 + ReLU + conv.2
     (+ F.normalize for cout = 2).  x [B,h1,w1,ld0]; w_packed / shift9 from models._pack_upconv (n = 16, no skip);

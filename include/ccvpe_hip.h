@@ -175,6 +175,16 @@ int ccvpe_upconv3x3_bf16(const ccvpe_upconv_desc* desc, void* stream);
 #define CCVPE_UPROUTE_DMA_PAIR 3 /* upconv_dma_kernel, two 8 x 8 images per tile (level 6) */
 #define CCVPE_UPROUTE_UP2 4      /* up2_kernel (bf16, narrow levels): four parities per workgroup, weights in registers */
 int ccvpe_upconv3x3_route(const ccvpe_upconv_desc* desc, int is_bf16);
+/* The same fp32 layer with its products on the bf16 matrix cores (csrc/upconv_s3.hip): every fp32 operand is split into three
+ * bf16 planes (hi + mid + lo == the fp32 value exactly) and x.w is summed from six plane products in fp32 — fp32-class error,
+ * not bit-identical to ccvpe_upconv3x3_f32.  desc as above (fp32 tensors, c1 > 0) except `w` / `kpad`: the three-plane pack
+ * [4][stages][npad16][hi 16 | mid 16 | lo 16] bf16 in the kernel's stage order (models._pack_upconv_s3), stages =
+ * 4*ceil(c0/16) + 9*ceil(c1/16), kpad = 48*stages.
+ * ccvpe_upconv3x3_s3_ok launches nothing: 0 = not served (no skip, low-res images narrower than 16 pixels other than 8 x 8,
+ * an n without a tile, a kpad that is not this pack's), 1 = computed correctly, 2 = and the measured size rule prefers it to
+ * ccvpe_upconv3x3_f32.  ccvpe_upconv3x3_s3_f32 runs every desc with _ok >= 1 and returns CCVPE_EINVAL otherwise. */
+int ccvpe_upconv3x3_s3_ok(const ccvpe_upconv_desc* desc);
+int ccvpe_upconv3x3_s3_f32(const ccvpe_upconv_desc* desc, void* stream);
 
 /* -------------------------------------------------------------------------------------------
  * The whole 512 x 512 level of a decoder in one launch (csrc/tail512.hip):
