@@ -95,6 +95,9 @@ PROTOTYPES = {
     "ccvpe_upconv3x3_route": (c_int, [ctypes.POINTER(UpconvDesc), c_int]),
     "ccvpe_upconv3x3_s3_ok": (c_int, [ctypes.POINTER(UpconvDesc)]),
     "ccvpe_upconv3x3_s3_f32": (c_int, [ctypes.POINTER(UpconvDesc), c_void_p]),
+    "ccvpe_upconv3x3_s3_form_ok": (c_int, [ctypes.POINTER(UpconvDesc), c_int]),
+    "ccvpe_upconv3x3_s3_form_f32": (c_int, [ctypes.POINTER(UpconvDesc), c_int, c_void_p]),
+    "ccvpe_set_s3_quad": (c_int, [c_int]),
     "ccvpe_stem_conv_f32": (c_int, [c_void_p] * 5 + [c_int] * 4 + [c_void_p]),
     "ccvpe_dwconv_nblk": (c_int, [c_int] * 4),
     "ccvpe_dwconv_f32": (c_int, [c_void_p] * 6 + [c_int] * 7 + [c_void_p]),
@@ -221,6 +224,8 @@ def load():
         lib.ccvpe_set_match_mfma(0)               # A/B runs: the vector-ALU matching kernel for every configuration
     if os.environ.get("CCVPE_PWN") == "0" and hasattr(lib, "ccvpe_set_pwn_kernels"):
         lib.ccvpe_set_pwn_kernels(0)              # A/B runs: the generic kernel for the narrow projections
+    if os.environ.get("CCVPE_S3_QUAD") == "0" and hasattr(lib, "ccvpe_set_s3_quad"):
+        lib.ccvpe_set_s3_quad(0)                  # A/B runs: the per-parity three-plane upconv kernel on every level
     if os.environ.get("CCVPE_MBPLANE") is not None and hasattr(lib, "ccvpe_set_mbconv_plane_kernels"):
         lib.ccvpe_set_mbconv_plane_kernels(int(os.environ["CCVPE_MBPLANE"]))   # A/B runs: 0 = pointwise GEMM + dwconv_plane_kernel
     _lib = lib

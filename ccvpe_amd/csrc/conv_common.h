@@ -287,5 +287,8 @@ int pwn_dispatch(const IgemmParams& p, int batch, int esz, hipStream_t stream);
 int up2_supported(int c0, int c1, int n, int kpad, int h1, int w1, int batch);
 int up2_dispatch(const void* src0, const void* src1, const void* w, const float* shift9, void* dst, int c0, int ld0, int c1, int ld1,
                  int h1, int w1, int n, int kpad, int ldd, int act, int batch, hipStream_t stream);
+// upconv_s3q.hip: the four-parities-per-workgroup form of upconv_s3.hip's layer, for a desc that file's checks have accepted
+bool upconv_s3q_serves(const ccvpe_upconv_desc* d);
+int upconv_s3q_launch(const ccvpe_upconv_desc* d, hipStream_t stream);
 
 }  // namespace ccvpe

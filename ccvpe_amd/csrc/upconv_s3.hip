@@ -403,11 +403,40 @@ extern "C" int ccvpe_upconv3x3_s3_ok(const ccvpe_upconv_desc* d) {
   return m >= 4096 ? 2 : 1;
 }
 
-extern "C" int ccvpe_upconv3x3_s3_f32(const ccvpe_upconv_desc* d, void* stream) {
+// Which form computes a served desc when the caller leaves the choice to the library (form 0).  Measured per level at B = 64 with
+// tools/up_probe.py (profiles/r11/up_probe.txt): the quad form (upconv_s3q.hip) beat the per-parity kernel in
+// isolation on all four levels it serves, by more than the spread of the probe's repetitions (quad / per-parity 0.79 at N = 32,
+// 0.81 at N = 40, 0.88 at N = 64, 0.96 at N = 80; spreads 0.01-0.04); nothing below 4096 low-res pixels was measured, so smaller
+// problems keep the per-parity kernel.
+static bool g_s3_quad = true;                     // ccvpe_set_s3_quad
+static int s3_auto_form(const ccvpe_upconv_desc* d) {
+  if (!g_s3_quad || !upconv_s3q_serves(d)) return 1;
+  const long m = (long)d->batch * d->h1 * d->w1;
+  return m >= 4096 ? 2 : 1;
+}
+
+extern "C" int ccvpe_set_s3_quad(int on) {
+  const int prev = g_s3_quad ? 1 : 0;
+  g_s3_quad = on != 0;
+  return prev;
+}
+
+extern "C" int ccvpe_upconv3x3_s3_form_ok(const ccvpe_upconv_desc* d, int form) {
+  if (s3_refusal(d)) return 0;
+  if (form == 0) return s3_auto_form(d);
+  if (form == 1) return 1;
+  if (form == 2) return upconv_s3q_serves(d) ? 2 : 0;
+  return 0;
+}
+
+static int s3_run(const ccvpe_upconv_desc* d, int form, void* stream) {
   if (const char* why = s3_refusal(d)) return fail(CCVPE_EINVAL, "upconv3x3_s3: %s", why);
+  if (form < 0 || form > 2) return fail(CCVPE_EINVAL, "upconv3x3_s3: form must be 0 (auto), 1 (per-parity) or 2 (quad)");
   if (!d->src0 || !d->src1 || !d->w || !d->shift9 || !d->dst) return fail(CCVPE_EINVAL, "upconv3x3_s3: null pointer");
   if (!aligned16(d->src0) || !aligned16(d->src1) || !aligned16(d->w) || !aligned16(d->dst))
     return fail(CCVPE_EINVAL, "upconv3x3_s3: pointers must be 16-byte aligned");
+  if (form == 0) form = s3_auto_form(d);
+  if (form == 2) return upconv_s3q_launch(d, (hipStream_t)stream);       // (refuses a desc the quad form does not serve)
   UpS3Params p;
   p.src0 = reinterpret_cast<const float*>(d->src0); p.src1 = reinterpret_cast<const float*>(d->src1);
   p.w = d->w; p.shift9 = d->shift9; p.dst = reinterpret_cast<float*>(d->dst);
@@ -426,3 +455,7 @@ extern "C" int ccvpe_upconv3x3_s3_f32(const ccvpe_upconv_desc* d, void* stream) 
 #undef CCVPE_CASE
   return fail(CCVPE_EINVAL, "upconv3x3_s3: no tile config");
 }
+
+extern "C" int ccvpe_upconv3x3_s3_f32(const ccvpe_upconv_desc* d, void* stream) { return s3_run(d, 0, stream); }
+
+extern "C" int ccvpe_upconv3x3_s3_form_f32(const ccvpe_upconv_desc* d, int form, void* stream) { return s3_run(d, form, stream); }

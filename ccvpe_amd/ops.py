@@ -340,11 +340,23 @@ def upconv3x3_s3_ok(src0, c0, w3_packed, n, *, batch, h1, w1, src1=None, c1=0, l
     return int(_lib.load().ccvpe_upconv3x3_s3_ok(ctypes.byref(d)))
 
 
+def upconv3x3_s3_form_ok(src0, c0, w3_packed, n, form, *, batch, h1, w1, src1=None, c1=0, ldd=None, ld0=None, ld1=None):
+    """ccvpe_upconv3x3_s3_form_ok: 0 = `form` (0 auto, 1 per-parity, 2 quad) cannot compute this layer, else the form that runs
+    (for form 0: what the library's size rule picks).  Nothing is launched."""
+    if not upconv3x3_s3_ok(src0, c0, w3_packed, n, batch=batch, h1=h1, w1=w1, src1=src1, c1=c1, ldd=ldd, ld0=ld0, ld1=ld1):
+        return 0
+    ld0 = ld0 if ld0 is not None else src0.shape[-1]
+    ld1 = ld1 if ld1 is not None else (src1.shape[-1] if src1 is not None else 0)
+    d = _s3_desc(src0, c0, w3_packed, None, n, batch, h1, w1, src1, c1, ACT_NONE, None, ldd if ldd is not None else n, ld0, ld1)
+    return int(_lib.load().ccvpe_upconv3x3_s3_form_ok(ctypes.byref(d), form))
+
+
 def upconv3x3_s3(src0, c0, w3_packed, shift9, n, *, batch, h1, w1, src1=None, c1=0, act=ACT_NONE, dst=None, ldd=None, ld0=None,
-                 ld1=None):
+                 ld1=None, form=None):
     """ccvpe_upconv3x3_f32's layer with its products on the bf16 matrix cores, three bf16 planes per fp32 operand
     (ccvpe_upconv3x3_s3_f32); w3_packed from models._pack_upconv_s3.  Same result as upconv3x3 to fp32 rounding, not bit for
-    bit.  fp32 tensors only; a layer the kernel does not serve is an error (no fallback)."""
+    bit.  fp32 tensors only; a layer the kernel does not serve is an error (no fallback).  form = None: the library chooses
+    between its per-parity and quad kernels (ccvpe_upconv3x3_s3_f32); 1 / 2 force one (ccvpe_upconv3x3_s3_form_f32)."""
     lib = _lib.load()
     for t, nm in ((src0, "src0"), (src1, "src1"), (shift9, "shift9"), (dst, "dst")):
         _chk(t, nm)
@@ -359,7 +371,10 @@ def upconv3x3_s3(src0, c0, w3_packed, shift9, n, *, batch, h1, w1, src1=None, c1
     d = _s3_desc(src0, c0, w3_packed, shift9, n, batch, h1, w1, src1, c1, act, dst, ldd, ld0, ld1)
     rec = _recorder
     ev0 = rec.begin() if rec is not None else None
-    check(lib.ccvpe_upconv3x3_s3_f32(ctypes.byref(d), _stream()), "ccvpe_upconv3x3_s3_f32")
+    if form is None:
+        check(lib.ccvpe_upconv3x3_s3_f32(ctypes.byref(d), _stream()), "ccvpe_upconv3x3_s3_f32")
+    else:
+        check(lib.ccvpe_upconv3x3_s3_form_f32(ctypes.byref(d), form, _stream()), "ccvpe_upconv3x3_s3_form_f32")
     if rec is not None:
         # the fp32 layer's FLOPs and bytes (as upconv3x3): this kernel's "TF" in the bench tables can exceed the fp32 peak
         m = batch * h1 * w1 * 4
@@ -368,6 +383,8 @@ def upconv3x3_s3(src0, c0, w3_packed, shift9, n, *, batch, h1, w1, src1=None, c1
         nbytes = 4.0 * (batch * h1 * w1 * c0 + m * c1 + m * n + 4 * n * k_eff)
         tile = igemm_tile(n).split("<")[1]
         name = "upconv_s3_kernel<%s%s" % (tile[:-1], ",pair>" if (h1 == 8 and w1 == 8) else ">")
+        if lib.ccvpe_upconv3x3_s3_form_ok(ctypes.byref(d), form or 0) == 2:
+            name = "upconv_s3q_kernel<2,%d>" % ((n + 15) // 16)
         rec.end(name, "up3x3 M%d N%d Keff%d" % (m, n, k_eff), flops, nbytes, ev0)
     return dst
 

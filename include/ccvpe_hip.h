@@ -185,6 +185,16 @@ int ccvpe_upconv3x3_route(const ccvpe_upconv_desc* desc, int is_bf16);
  * ccvpe_upconv3x3_f32.  ccvpe_upconv3x3_s3_f32 runs every desc with _ok >= 1 and returns CCVPE_EINVAL otherwise. */
 int ccvpe_upconv3x3_s3_ok(const ccvpe_upconv_desc* desc);
 int ccvpe_upconv3x3_s3_f32(const ccvpe_upconv_desc* desc, void* stream);
+/* Two forms compute that layer: 1 = one output parity per workgroup (csrc/upconv_s3.hip, every served desc), 2 = "quad", all four
+ * parities per workgroup (csrc/upconv_s3q.hip: 16 < n <= 80, images of 16 or more pixels a row; bit-identical to form 1 when
+ * c1 <= 16).  ccvpe_upconv3x3_s3_f32 chooses by a measured size rule (form 0 = auto).
+ * ccvpe_upconv3x3_s3_form_ok launches nothing: 0 = `form` cannot compute the desc, else the form that runs (for form 0: what
+ * auto picks, 1 or 2).  ccvpe_upconv3x3_s3_form_f32 forces a form (0 = auto) and returns CCVPE_EINVAL for one that cannot serve
+ * the desc.  ccvpe_set_s3_quad(0) makes auto never choose form 2 (A/B runs; the binding calls it for CCVPE_S3_QUAD=0); the
+ * forcing entry point ignores it.  Returns the previous setting. */
+int ccvpe_upconv3x3_s3_form_ok(const ccvpe_upconv_desc* desc, int form);
+int ccvpe_upconv3x3_s3_form_f32(const ccvpe_upconv_desc* desc, int form, void* stream);
+int ccvpe_set_s3_quad(int on);
 
 /* -------------------------------------------------------------------------------------------
  * The whole 512 x 512 level of a decoder in one launch (csrc/tail512.hip):

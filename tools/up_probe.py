@@ -1,6 +1,8 @@
 """Micro-probe of the folded deconv + 3x3 kernels on the decoder's shapes: python tools/up_probe.py [reps] [bf16]
 In fp32 every shape with a skip is also timed through the three-plane bf16 kernel (ccvpe_upconv3x3_s3_f32, whatever its size
-rule says): the per-level table of DESIGN section 4 and the rule in csrc/upconv_s3.hip come from this output.
+rule says): the per-level table of DESIGN section 4 and the rule in csrc/upconv_s3.hip come from this output.  Where the quad
+form (csrc/upconv_s3q.hip) serves the shape, the per-parity form (s3) and the quad form (s3q) are timed side by side, three
+passes of `reps` launches each after an untimed one, alternating: q/p = ratio of the medians, spread = the larger (max - min) / median of the two.
 """
 import os
 import sys
@@ -46,6 +48,20 @@ for (b, h1, c0, c1, n) in shapes:
     w3 = models._pack_upconv_s3(w, c0, c1, dt)
     ok = ops.upconv3x3_s3_ok(x, c0, w3, n, batch=b, h1=h1, w1=h1, src1=sk, c1=c1)
     if ok:
-        ms3 = timed(lambda: ops.upconv3x3_s3(x, c0, w3, sh, n, batch=b, h1=h1, w1=h1, src1=sk, c1=c1, act=ops.ACT_RELU))
+        run3 = lambda form: ops.upconv3x3_s3(x, c0, w3, sh, n, batch=b, h1=h1, w1=h1, src1=sk, c1=c1, act=ops.ACT_RELU, form=form)
+        quad = ops.upconv3x3_s3_form_ok(x, c0, w3, n, 2, batch=b, h1=h1, w1=h1, src1=sk, c1=c1) == 2
+        tp, tq = [], []
+        if quad:
+            timed(lambda: run3(1)), timed(lambda: run3(2))          # one untimed pass of each: clocks and caches settle
+        for _ in range(3 if quad else 1):
+            tp.append(timed(lambda: run3(1)))
+            if quad:
+                tq.append(timed(lambda: run3(2)))
+        ms3 = sorted(tp)[len(tp) // 2]
         line += "  | s3 %9.1f us %7.1f TF  x%.2f  ok=%d" % (ms3 * 1e3, 2.0 * m * n * k / ms3 / 1e9, ms / ms3, ok)
+        if quad:
+            msq = sorted(tq)[1]
+            spread = max((max(t) - min(t)) / sorted(t)[1] for t in (tp, tq))
+            auto = ops.upconv3x3_s3_form_ok(x, c0, w3, n, 0, batch=b, h1=h1, w1=h1, src1=sk, c1=c1)
+            line += "  | s3q %9.1f us %7.1f TF  q/p %.3f  spread %.3f  auto=%d" % (msq * 1e3, 2.0 * m * n * k / msq / 1e9, msq / ms3, spread, auto)
     print(line, flush=True)
