@@ -35,6 +35,19 @@
 // and per 16 channels two v_mfma_f32_16x16x32_bf16 — A = [w_hi | w_hi] then A = [w_lo | 0] against B = [x_hi | x_lo] — instead
 // of four v_mfma_f32_16x16x4_f32: 32 instead of 128 matrix cycles.  Logit error ~1e-5 of scale (tests/test_ops_gpu.py) where
 // bf16 storage of the same operands gives 4e-3: the arg-max of the bf16 path is decided exactly as with the fp32 tail.
+// The template parameter SPLIT is the PLANE COUNT: 0 (none), 2 (the above; ccvpe_tail_desc.split == 1) or 3 (desc.split == 2):
+//
+// SPLIT == 3 (the fp32 path's tails, both decoders): three planes per operand, hi = bf16(v), mid = bf16(v - hi), lo = bf16(v - hi -
+// mid), v == hi + mid + lo, and the six products hh, hm, mh, mm, hl, lh of csrc/upconv_s3.hip (ml, lm, ll dropped: each <= 2^-24
+// |x||w|), fp32 accumulate in a fixed order: fp32-class results at 48 instead of 128 matrix cycles per 16 channels.  W is split
+// here, once per persistent workgroup, from the same fp32 pack; x is split at the LDS store into the pixel row [hi 0..15 | mid
+// 0..15 | lo 0..15] = all 96 bytes of the wide slot (no LDS growth).  Of the two arrangements that give the six products
+//   (I)  A = [w_hi|w_hi], [w_mid|w_mid], [w_hi|w_lo]   B = [x_hi|x_mid] (twice), [x_lo|x_hi]    12 W registers, 2 ds_read_b128
+//   (II) A = [w_hi|w_mid] (twice), [w_hi|w_lo]         B = [x_hi|x_hi], [x_mid|x_mid], [x_lo|x_hi]   8 W registers, 3 ds_read_b128
+// this kernel takes (II): W is 96 registers at 41 channels as in the two-plane mode ((I): 144, which leaves no room for the 40
+// accumulators of the 8 x 16 tile under the 256 of two workgroups per CU); lane groups 2, 3 re-read the bytes of groups 0, 1 in
+// the first two fragments.  Every fragment read is the two-plane read moved by a multiple of 32 bytes, so the 96-byte slot in rows of
+// 25 stays conflict-free in the bank model (tests/test_lds_layout_tail3.py).  conv.2's weights wait in LDS, not in registers.
 #include "conv_common.h"
 
 namespace ccvpe {
@@ -51,7 +64,7 @@ struct TailParams {
   int tiles_x, tiles_y, tiles_total, tiles_per_wg;
 };
 
-template <typename T, int COUT, int NCH, int TY, int TX, int WPP, bool SPLIT = false, bool PERSIST = false>
+template <typename T, int COUT, int NCH, int TY, int TX, int WPP, int SPLIT = 0, bool PERSIST = false>
 struct TailGeom {
   static constexpr int NW = 4 * WPP;
   static constexpr int NTHR = 64 * NW;
@@ -67,7 +80,10 @@ struct TailGeom {
   // 96-byte slots in rows of 25 (SQ_LDS_BANK_CONFLICT / SQ_ACTIVE_INST_LDS of the bf16-path tails: 1.5-2.1 with the LDS pipe
   // 35 % busy, tools/gpu/lds_pmc.sh).  It costs 67 % more LDS per chunk buffer, so the latency-shaped 8 x 16 tiles of the bf16
   // storage path take it (48 KB per workgroup) and the matrix-bound 16 x 16 fp32 tile (which would need 86 KB) keeps the 80-byte slot.
-  static constexpr bool WIDE_SLOT = TY == 8 && TX == 16 && (SPLIT || sizeof(T) == 2);
+  static constexpr bool WIDE_SLOT = TY == 8 && TX == 16 && (SPLIT != 0 || sizeof(T) == 2);
+  // SPLIT == 3 fills all 96 bytes of the wide slot ([hi | mid | lo]) and reads it at three plane offsets; every one of those reads
+  // is the two-plane read rotated by a multiple of 32 bytes, so the same geometry stays conflict-free (tests/test_lds_layout_tail3.py)
+  static_assert(SPLIT != 3 || WIDE_SLOT, "three planes need the 96-byte slot");
   static constexpr int LD = WIDE_SLOT ? 24 : 20;     // floats per staged pixel slot
   static constexpr int HCP = WIDE_SLOT ? 25 : HC;    // slots per halo row
   static constexpr int XBUF = HR * HCP * LD;         // floats per x chunk buffer
@@ -75,7 +91,8 @@ struct TailGeom {
   static constexpr int SH = 2 * TY + 2, SW = 2 * TX + 2, SPL = SH * SW;   // one tap plane of the mid grid
   static constexpr int NPL = 10;                     // 9 tap planes + one junk plane (lanes whose tap index is >= 9 store there)
   static constexpr int MAIN = (NXB * XBUF > NPL * SPL) ? NXB * XBUF : NPL * SPL;
-  static constexpr int LDS_BYTES = (MAIN + 9 * 16) * 4;
+  static constexpr int W2S = SPLIT == 3 ? COUT * 9 * 16 : 0;   // SPLIT == 3 keeps conv.2's weights in LDS, not in registers across the matrix loop
+  static constexpr int LDS_BYTES = (MAIN + 9 * 16 + W2S) * 4;
   static constexpr int NOUT = (4 * TY * TX) / NTHR;  // outputs per thread in stage 3
 };
 
@@ -88,8 +105,20 @@ __device__ __forceinline__ void split4(f32x4 v, bf16x4& hi, bf16x4& lo) {
   }
 }
 
-template <typename T, int COUT, int NCH, int TY, int TX, int WPP, bool SPLIT, bool PERSIST>
+// hi / mid / lo bf16 planes of 4 fp32 values (SPLIT == 3): both subtractions are exact in fp32, v == hi + mid + lo
+__device__ __forceinline__ void split4x3(f32x4 v, bf16x4& hi, bf16x4& mid, bf16x4& lo) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    hi[i] = (bf16_t)v[i];
+    const float r = v[i] - (float)hi[i];
+    mid[i] = (bf16_t)r;
+    lo[i] = (bf16_t)(r - (float)mid[i]);
+  }
+}
+
+template <typename T, int COUT, int NCH, int TY, int TX, int WPP, int SPLIT, bool PERSIST>
 __global__ __launch_bounds__(256 * WPP, 2) void tail512_kernel(const TailParams p) {
+  static_assert(SPLIT == 0 || SPLIT == 2 || SPLIT == 3, "SPLIT is a plane count");
   static_assert(!SPLIT || sizeof(T) == 4, "SPLIT reads fp32 operands");
   using G = TailGeom<T, COUT, NCH, TY, TX, WPP, SPLIT, PERSIST>;
   constexpr int E = ElemTraits<T>::E;
@@ -135,9 +164,12 @@ __global__ __launch_bounds__(256 * WPP, 2) void tail512_kernel(const TailParams 
   const T* xg = reinterpret_cast<const T*>(p.x);
 
   for (int i = tid; i < 9 * 16; i += NTHR) Sh9[i] = p.shift9[i];
+  [[maybe_unused]] float* W2s = Sh9 + 9 * 16;        // [COUT][9][16] (SPLIT == 3)
+  if constexpr (SPLIT == 3)
+    for (int i = tid; i < G::W2S; i += NTHR) W2s[i] = p.w2[i];
 
   // ---- W of this wave's parity: MFMA A-fragments in registers ------------------------------------------------------
-  constexpr int NWR = SPLIT ? 2 : 1;                 // SPLIT: [0] = [w_hi | w_hi], [1] = [w_lo | 0]
+  constexpr int NWR = SPLIT ? 2 : 1;                 // SPLIT 2: [0] = [w_hi | w_hi], [1] = [w_lo | 0];  3: [0] = [w_hi | w_mid], [1] = [w_hi | w_lo]
   f32x4 wr[4][NCH][NWR];
   if constexpr (!SPLIT) {
     const T* wp = reinterpret_cast<const T*>(p.w) + ((size_t)par * 16 + pix) * p.Kpad;
@@ -164,6 +196,22 @@ __global__ __launch_bounds__(256 * WPP, 2) void tail512_kernel(const TailParams 
         const bool ok = ch < p.c0;                     // c0 % 8 == 0: the 8 channels are in range together
         const f32x4 v0 = keep_if(*reinterpret_cast<const f32x4*>(wp + (ok ? tap * p.c0 + ch : 0)), ok);
         const f32x4 v1 = keep_if(*reinterpret_cast<const f32x4*>(wp + (ok ? tap * p.c0 + ch + 4 : 0)), ok);
+        if constexpr (SPLIT == 3) {
+          // lane groups 0, 1 hold w_hi in both fragments; groups 2, 3 hold w_mid in [0] and w_lo in [1]
+          bf16x4 h0, m0, l0, h1, m1, l1;
+          split4x3(v0, h0, m0, l0);
+          split4x3(v1, h1, m1, l1);
+          bf16x8 f0, f1;
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            f0[i] = q < 2 ? h0[i] : m0[i];
+            f0[i + 4] = q < 2 ? h1[i] : m1[i];
+            f1[i] = q < 2 ? h0[i] : l0[i];
+            f1[i + 4] = q < 2 ? h1[i] : l1[i];
+          }
+          wr[tap][c][0] = __builtin_bit_cast(f32x4, f0);
+          wr[tap][c][1] = __builtin_bit_cast(f32x4, f1);
+        } else {
         bf16x4 h0, l0, h1, l1;
         split4(v0, h0, l0);
         split4(v1, h1, l1);
@@ -172,13 +220,16 @@ __global__ __launch_bounds__(256 * WPP, 2) void tail512_kernel(const TailParams 
         for (int i = 0; i < 4; ++i) { hi[i] = h0[i]; hi[i + 4] = h1[i]; lo[i] = l0[i]; lo[i + 4] = l1[i]; }
         wr[tap][c][0] = __builtin_bit_cast(f32x4, hi);
         wr[tap][c][1] = keep_if(__builtin_bit_cast(f32x4, lo), q < 2);
+        }
       }
   }
   // conv.2 as [tap][channel]: lane (tap = pix, q) holds channels 4q .. 4q+3 of output o
   f32x4 w2f[COUT];
+  if constexpr (SPLIT != 3) {
 #pragma unroll
-  for (int o = 0; o < COUT; ++o) {
-    w2f[o] = keep_if(*reinterpret_cast<const f32x4*>(p.w2 + (o * 9 + min(pix, 8)) * 16 + q * 4), pix < 9);
+    for (int o = 0; o < COUT; ++o) {
+      w2f[o] = keep_if(*reinterpret_cast<const f32x4*>(p.w2 + (o * 9 + min(pix, 8)) * 16 + q * 4), pix < 9);
+    }
   }
 
   // ---- halo staging: thread -> (halo pixel, 16-byte piece); coordinates are recomputed per chunk (NCH <= 3 times) rather
@@ -212,6 +263,15 @@ __global__ __launch_bounds__(256 * WPP, 2) void tail512_kernel(const TailParams 
       const f32x4 v = keep_if(h_reg[it], (h_keep >> it) & 1u);
       if constexpr (!SPLIT) {
         if (pxl < HPX) *reinterpret_cast<f32x4*>(Xs + buf * XBUF + slot * LD + hsub * 4) = v;
+      } else if constexpr (SPLIT == 3) {             // row = [hi 0..15 | mid 0..15 | lo 0..15] bf16: 8 + 8 + 8 bytes of the 96
+        bf16x4 hi, mid, lo;
+        split4x3(v, hi, mid, lo);
+        if (pxl < HPX) {
+          bf16_t* row = reinterpret_cast<bf16_t*>(Xs + buf * XBUF + slot * LD);
+          *reinterpret_cast<bf16x4*>(row + hsub * 4) = hi;
+          *reinterpret_cast<bf16x4*>(row + 16 + hsub * 4) = mid;
+          *reinterpret_cast<bf16x4*>(row + 32 + hsub * 4) = lo;
+        }
       } else {                                       // row = [hi 0..15 | lo 0..15] bf16: this piece's 4 channels -> 8 + 8 bytes
         bf16x4 hi, lo;
         split4(v, hi, lo);
@@ -238,8 +298,11 @@ __global__ __launch_bounds__(256 * WPP, 2) void tail512_kernel(const TailParams 
   for (int i = 0; i < TPW; ++i) {
     const int pc = min((wsub * TPW + i) * 16 + pixv, P - 1);
     const int iy = pc / PW, ix = pc - iy * PW;
-    fbase[i] = (iy * HCP + ix) * LD + qv * 4;
+    fbase[i] = (iy * HCP + ix) * LD + (SPLIT == 3 ? qv & 1 : qv) * 4;
   }
+  // SPLIT == 3, arrangement (II): B fragments [x_hi | x_hi] at fbase, [x_mid | x_mid] at fbase + 32 bytes, [x_lo | x_hi] at
+  // fbase + 64 bytes for lane groups 0, 1 and at fbase for groups 2, 3
+  [[maybe_unused]] const int f3off = qv < 2 ? 16 : 0;
   f32x4 acc[TPW];
 #pragma unroll
   for (int i = 0; i < TPW; ++i) acc[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -264,6 +327,32 @@ __global__ __launch_bounds__(256 * WPP, 2) void tail512_kernel(const TailParams 
       dst[0] = *reinterpret_cast<const f32x4*>(xb + fbase[2 * g] + toff);
       if (2 * g + 1 < TPW) dst[1] = *reinterpret_cast<const f32x4*>(xb + fbase[2 * g + 1] + toff);
     };
+    if constexpr (SPLIT == 3) {
+      // a step is (pair of position tiles, tap, fragment h): two MFMAs.  Three fragment buffers, read TWO steps ahead — the same
+      // four MFMAs of cover as the two-plane loop in 24 registers; holding all three fragments of a tap twice over (48) put
+      // the 41-channel instantiation into scratch.  Six products per 16 channels in a fixed order:
+      //   h = 0: [w_hi | w_mid].[x_hi | x_hi]    h = 1: [w_hi | w_mid].[x_mid | x_mid]    h = 2: [w_hi | w_lo].[x_lo | x_hi]
+      constexpr int NU = NS * 3;
+      f32x4 fb[3][2];
+      auto read_sub = [&](int u, f32x4* dst) {
+        const int g = u / 12, tap = (u / 3) & 3, h = u % 3;
+        const int toff = ((tap >> 1) * HCP + (tap & 1)) * LD + (h == 1 ? 8 : 0);
+        const int lane_off = h == 2 ? f3off : 0;
+        dst[0] = *reinterpret_cast<const f32x4*>(xb + fbase[2 * g] + lane_off + toff);
+        if (2 * g + 1 < TPW) dst[1] = *reinterpret_cast<const f32x4*>(xb + fbase[2 * g + 1] + lane_off + toff);
+      };
+      read_sub(0, fb[0]);
+      read_sub(1, fb[1]);
+#pragma unroll
+      for (int u = 0; u < NU; ++u) {
+        const int g = u / 12, tap = (u / 3) & 3, h = u % 3;
+        if (u + 2 < NU) read_sub(u + 2, fb[(u + 2) % 3]);
+        __builtin_amdgcn_sched_barrier(0);
+        acc[2 * g] = mfma_stage<bf16_t>(wr[tap][c][h >> 1], fb[u % 3][0], acc[2 * g]);
+        if (2 * g + 1 < TPW) acc[2 * g + 1] = mfma_stage<bf16_t>(wr[tap][c][h >> 1], fb[u % 3][1], acc[2 * g + 1]);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    } else {
     read_step(0, fr[0]);
 #pragma unroll
     for (int s = 0; s < NS; ++s) {
@@ -272,7 +361,7 @@ __global__ __launch_bounds__(256 * WPP, 2) void tail512_kernel(const TailParams 
       __builtin_amdgcn_sched_barrier(0);             // the reads above stay above this step's MFMAs
       const f32x4 wv = wr[tap][c][0];
       const f32x4 f0 = fr[s & 1][0], f1 = fr[s & 1][1];
-      if constexpr (SPLIT) {
+      if constexpr (SPLIT == 2) {
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
           acc[2 * g] = mfma_stage<bf16_t>(wr[tap][c][h], f0, acc[2 * g]);
@@ -289,6 +378,7 @@ __global__ __launch_bounds__(256 * WPP, 2) void tail512_kernel(const TailParams 
         if (2 * g + 1 < TPW) acc[2 * g + 1] = mfma_stage<T>(wv, f1, acc[2 * g + 1]);
       }
       __builtin_amdgcn_sched_barrier(0);
+    }
     }
     if (c + 1 < NCH) {
       store_halo((c + 1) & 1);
@@ -319,6 +409,11 @@ __global__ __launch_bounds__(256 * WPP, 2) void tail512_kernel(const TailParams 
     for (int r = 0; r < 4; ++r) acc[i][r] = inside ? fmaxf(acc[i][r] + sh[r], 0.f) : 0.f;
   }
   float res[COUT][G::NOUT];
+  if constexpr (SPLIT == 3) {                        // (the same fragments as above, fetched per tile: the 96 W registers, the
+#pragma unroll                                       //  accumulators and the staging registers leave no room to hold them)
+    for (int o = 0; o < COUT; ++o)
+      w2f[o] = keep_if(*reinterpret_cast<const f32x4*>(W2s + (o * 9 + min(pixv, 8)) * 16 + qv * 4), pixv < 9);
+  }
 #pragma unroll
   for (int o = 0; o < COUT; ++o) {
 #pragma unroll
@@ -384,7 +479,7 @@ __global__ __launch_bounds__(256 * WPP, 2) void tail512_kernel(const TailParams 
   }  // tile loop
 }
 
-template <typename T, int COUT, int NCH, int TY, int TX, int WPP, bool SPLIT = false, bool PERSIST = false>
+template <typename T, int COUT, int NCH, int TY, int TX, int WPP, int SPLIT = 0, bool PERSIST = false>
 static int launch_tail(const TailParams& p0, int batch, hipStream_t stream) {
   using G = TailGeom<T, COUT, NCH, TY, TX, WPP, SPLIT, PERSIST>;
   TailParams p = p0;
@@ -432,19 +527,26 @@ static int tail_any(const ccvpe_tail_desc* d, void* stream) {
   // Workgroup tile, fp32: 16 x 16 low-res pixels, one wave per parity, one tile per workgroup, two workgroups per CU (a workgroup's
   // stage 2/3 runs under the other's matrix loop).  Measured against 32 x 16 with two waves per parity and one workgroup per CU
   // (B = 64, tools/tail_probe.py): fp32 loc 1.11 vs 1.23 ms, fp32 ori 0.95 vs 1.01 — the smaller apron does not pay for the lost
-  // overlap.  bf16 / SPLIT: 8 x 16 tiles walked by persistent workgroups (see the kernel's PERSIST comment).
+  // overlap.  bf16 / SPLIT (two and three planes): 8 x 16 tiles walked by persistent workgroups (see the kernel's PERSIST comment).
 #define CCVPE_TAIL(COUT_, NCH_)                                                                                \
   if (d->cout == COUT_ && nch == NCH_) {                                                                       \
-    if constexpr (sizeof(T) == 4) return launch_tail<T, COUT_, NCH_, 16, 16, 1, false, false>(p, d->batch, st); \
-    else return launch_tail<T, COUT_, NCH_, 8, 16, 1, false, true>(p, d->batch, st);                           \
+    if constexpr (sizeof(T) == 4) return launch_tail<T, COUT_, NCH_, 16, 16, 1, 0, false>(p, d->batch, st); \
+    else return launch_tail<T, COUT_, NCH_, 8, 16, 1, 0, true>(p, d->batch, st);                           \
   }
   if constexpr (sizeof(T) == 4) {
-    if (d->split) {                                           // fp32 operands, bf16 hi/lo matrix arithmetic (bf16 storage path only)
+    if (d->split == 1) {                                      // fp32 operands, bf16 hi/lo matrix arithmetic (bf16 storage path only)
       // (8 x 16 tile: the hi and lo W fragments are 96 registers at 41 channels, so the accumulators get half the tile)
-      if (d->cout == 1 && nch == 2) return launch_tail<T, 1, 2, 8, 16, 1, true, true>(p, d->batch, st);
-      if (d->cout == 1 && nch == 3) return launch_tail<T, 1, 3, 8, 16, 1, true, true>(p, d->batch, st);
-      return fail(CCVPE_EINVAL, "tail512: split mode is instantiated for cout 1, 17..48 channels");
+      if (d->cout == 1 && nch == 2) return launch_tail<T, 1, 2, 8, 16, 1, 2, true>(p, d->batch, st);
+      if (d->cout == 1 && nch == 3) return launch_tail<T, 1, 3, 8, 16, 1, 2, true>(p, d->batch, st);
+      return fail(CCVPE_EINVAL, "tail512: split mode 1 is instantiated for cout 1, 17..48 channels");
     }
+    if (d->split == 2) {                                      // three bf16 planes per operand, six products: the fp32 path's tails
+      if (d->cout == 1 && nch == 2) return launch_tail<T, 1, 2, 8, 16, 1, 3, true>(p, d->batch, st);
+      if (d->cout == 1 && nch == 3) return launch_tail<T, 1, 3, 8, 16, 1, 3, true>(p, d->batch, st);
+      if (d->cout == 2 && nch == 2) return launch_tail<T, 2, 2, 8, 16, 1, 3, true>(p, d->batch, st);
+      return fail(CCVPE_EINVAL, "tail512: split mode 2 is instantiated for cout 1 with 17..48 channels and cout 2 with 17..32");
+    }
+    if (d->split) return fail(CCVPE_EINVAL, "tail512: split must be 0, 1 or 2 (got %d)", d->split);
     CCVPE_TAIL(1, 2) CCVPE_TAIL(1, 3) CCVPE_TAIL(2, 2)      // loc: 33 / 41 channels (ld 40 / 48); ori: 32
   } else {
     if (d->split) return fail(CCVPE_EINVAL, "tail512: split mode takes fp32 operands");
@@ -459,7 +561,7 @@ static int tail_any(const ccvpe_tail_desc* d, void* stream) {
 template <typename T>
 static int tail_partials(const ccvpe_tail_desc* d) {
   if (!d || d->h1 <= 0 || d->w1 <= 0) return fail(CCVPE_EINVAL, "tail512_partials: bad desc");
-  const bool small = sizeof(T) == 2 || d->split;                 // 8 x 16 tiles (bf16, split), 16 x 16 otherwise; 4 waves
+  const bool small = sizeof(T) == 2 || d->split;                 // 8 x 16 tiles (bf16, split 1 and 2), 16 x 16 otherwise; 4 waves
   const int ty = small ? 8 : 16;
   if (d->h1 % ty || d->w1 % 16) return fail(CCVPE_EINVAL, "tail512_partials: shape not tiled");
   return (d->h1 / ty) * (d->w1 / 16) * 4;

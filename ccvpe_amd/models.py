@@ -190,6 +190,9 @@ WINO = __import__("os").environ.get("CCVPE_WINO", "1") != "0"
 # fp32 folded deconv + conv.0 layers on the bf16 matrix cores with three bf16 planes per operand where the library's size rule prefers
 # it (csrc/upconv_s3.hip); CCVPE_SPLIT3=0 = the fp32 kernels (A/B runs)
 SPLIT3 = __import__("os").environ.get("CCVPE_SPLIT3", "1") != "0"
+# ... and the two fused 512 x 512 tails of the fp32 path the same way (csrc/tail512.hip, split = 2: W and x split in the kernel, no new
+# pack); CCVPE_SPLIT3_TAIL=0 = exact fp32 tails (A/B runs), CCVPE_SPLIT3=0 switches it off as well
+SPLIT3_TAIL = SPLIT3 and __import__("os").environ.get("CCVPE_SPLIT3_TAIL", "1") != "0"
 SPLIT3_MIN_OK = 2          # ccvpe_upconv3x3_s3_ok value a layer needs for the route (tests open the size rule with 1)
 # train mode: replay the per-step weight re-pack as one hipGraph (see _CVMBase._packed); CCVPE_PACK_GRAPH=0 keeps it eager
 PACK_GRAPH = __import__("os").environ.get("CCVPE_PACK_GRAPH", "1") != "0"
@@ -202,6 +205,16 @@ FUSE_STEM = __import__("os").environ.get("CCVPE_FUSE_STEM", "1") != "0"
 # eval forward: CCVPE_EVAL_TWO_STREAMS=0 runs the ground encoder on the main stream too (for per-kernel profiles in which no
 # two kernels share the chip; the default overlaps the two encoders)
 EVAL_TWO_STREAMS = __import__("os").environ.get("CCVPE_EVAL_TWO_STREAMS", "1") != "0"
+
+
+def _tail_split(precision, x, cout):
+    """ops.tail512's `split` for a tail whose input is x: 1 = the fp32 tail of the bf16 storage path (two bf16 planes, served for
+    cout 1 only), 2 = the fp32 path (three planes), 0 = the element type's own matrix arithmetic."""
+    if x.dtype != torch.float32:
+        return 0
+    if precision == "bf16":
+        return 1 if SPLIT_TAIL and cout == 1 else 0
+    return 2 if SPLIT3 and SPLIT3_TAIL else 0
 
 
 def _pack_upconv(wd, bd, col_map, cp, w3, b3, dtype=torch.float32):
@@ -649,7 +662,8 @@ class _CVMBase(nn.Module):
             skip = sfeats[SKIP_BLOCKS[j]] if j < 5 else None
             if j == 5 and FUSE_TAIL and j in FOLD_LEVELS and ops.tail512_ok(hw, hw, ov.n_a):
                 # the whole 512 x 512 level in one launch: deconv1_ori + conv1_ori + F.normalize (models.py:145-148,341)
-                return ops.tail512(xo, ov.k, ov.fw, ov.fshift, ov.w_b, ov.b_b, 2, normalize, batch=batch, h1=hw, w1=hw)
+                return ops.tail512(xo, ov.k, ov.fw, ov.fshift, ov.w_b, ov.b_b, 2, normalize, batch=batch, h1=hw, w1=hw,
+                                   split=_tail_split(self.precision, xo, 2))
             if j in FOLD_LEVELS and batch * hw * hw >= FOLD_MIN_PIXELS:
                 y = _upconv_a(ov, xo, ov.k, batch, hw, skip)
             else:
@@ -784,9 +798,9 @@ class _CVMBase(nn.Module):
                 if j == 5 and FUSE_TAIL and j in FOLD_LEVELS and ops.tail512_ok(hw, hw, lv.n_a):
                     # the whole 512 x 512 level in one launch: deconv1 + conv1 -> logits (models.py:124-127,319)
                     # (bf16 storage path: its fp32 tail multiplies on the bf16 matrix cores with hi + lo operand planes — fp32-class
-                    # accuracy at a quarter of the matrix cycles; the fp32 path is exact fp32)
+                    # accuracy at a quarter of the matrix cycles; the fp32 path: three planes, six products, SPLIT3_TAIL)
                     logits_map, smx = ops.tail512(cat, lv.ldo, lv.fw, lv.fshift, lv.w_b, lv.b_b, 1, False, batch=batch, h1=hw, w1=hw,
-                                                  split=(self.precision == "bf16" and cat.dtype == torch.float32 and SPLIT_TAIL),
+                                                  split=_tail_split(self.precision, cat, 1),
                                                   want_softmax=True)
                     break
                 if j in FOLD_LEVELS and batch * hw * hw >= FOLD_MIN_PIXELS:   # deconv folded into conv.0: one GEMM per output parity

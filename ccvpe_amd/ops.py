@@ -392,7 +392,9 @@ def upconv3x3_s3(src0, c0, w3_packed, shift9, n, *, batch, h1, w1, src1=None, c1
 def tail512(x, c0, w_packed, shift9, w2, b2, cout, normalize, *, batch, h1, w1, split=False, want_softmax=False):
     """The whole 512 x 512 decoder level in one launch (ccvpe_tail512_f32 / _bf16): folded deconv + conv.0 + ReLU + conv.2
     (+ F.normalize for cout = 2).  x [B,h1,w1,ld0]; w_packed / shift9 from models._pack_upconv (n = 16, no skip);
-    w2 [cout,3,3,16], b2 [cout] fp32; returns [B,cout,2h1,2w1] fp32."""
+    w2 [cout,3,3,16], b2 [cout] fp32; returns [B,cout,2h1,2w1] fp32.
+    split (fp32 operands): 0 / False = exact fp32 products; 1 / True = two bf16 planes per operand (cout 1: the fp32 tail of the bf16
+    storage path); 2 = three bf16 planes, six products, fp32-class (cout 1 and 2: the fp32 path)."""
     lib = _lib.load()
     dt = _act_dtype(x)
     _chk(x, "x", dt)
@@ -406,7 +408,8 @@ def tail512(x, c0, w_packed, shift9, w2, b2, cout, normalize, *, batch, h1, w1, 
     d.x, d.w, d.shift9, d.w2, d.b2, d.out = _ptr(x), _ptr(w_packed), _ptr(shift9), _ptr(w2), _ptr(b2), _ptr(out)
     d.batch, d.h1, d.w1 = batch, h1, w1
     d.c0, d.ld0, d.kpad = c0, x.shape[-1], w_packed.shape[-1]
-    d.cout, d.normalize, d.split = cout, int(bool(normalize)), int(bool(split))
+    split = int(split)                       # True -> 1
+    d.cout, d.normalize, d.split = cout, int(bool(normalize)), split
     smx = None
     if want_softmax:                         # cout = 1: per-(tile, wave) softmax partials for softmax_apply()
         npart = lib.ccvpe_tail512_partials(ctypes.byref(d), int(dt != torch.float32))
@@ -421,7 +424,7 @@ def tail512(x, c0, w_packed, shift9, w2, b2, cout, normalize, *, batch, h1, w1, 
     if rec is not None:
         m = batch * h1 * w1 * 4
         esz = 4.0 if dt == torch.float32 else 2.0
-        rec.end("tail512_kernel<%s,%d>" % (("f32" if not split else "f32 as bf16 hi+lo") if dt == torch.float32 else "bf16", cout), "tail M%d Keff%d" % (m, 4 * c0),
+        rec.end("tail512_kernel<%s,%d>" % (("f32", "f32 as bf16 hi+lo", "f32 as bf16 hi+mid+lo")[split] if dt == torch.float32 else "bf16", cout), "tail M%d Keff%d" % (m, 4 * c0),
                 2.0 * m * 16 * (4 * c0 + 9 * cout), esz * batch * h1 * w1 * c0 + 4.0 * m * cout, ev0)
     return (out, smx) if want_softmax else out
 

@@ -204,9 +204,13 @@ int ccvpe_set_s3_quad(int on);
  * with n = 16 and c1 = 0 ([4][16][kpad], [9][16]), w2 [cout][3][3][16] fp32, b2 [cout], out [B,cout,2h1,2w1] fp32
  * (NCHW).  The 16-channel intermediate is never written.  h1, w1 multiples of 16.  Same results as ccvpe_upconv3x3 +
  * ccvpe_head_conv3x3 (fp32: to rounding; bf16: better — the intermediate is not rounded to bf16).
- * split (ccvpe_tail512_f32 only, cout = 1): 0 = exact fp32 matrix arithmetic; 1 = the fp32 operands are split into bf16 hi + lo
+ * split (ccvpe_tail512_f32 only): 0 = exact fp32 matrix arithmetic; 1 (cout = 1 only) = the fp32 operands are split into bf16 hi + lo
  * planes and multiplied on the bf16 matrix cores (hi.hi + lo.hi + hi.lo, fp32 accumulate: ~1e-5 of scale instead of bit-level
- * fp32) — the fp32 tail of the bf16 STORAGE path (set_precision("bf16")), never used by the fp32 path.
+ * fp32) — the fp32 tail of the bf16 STORAGE path (set_precision("bf16")), never used by the fp32 path; 2 (cout = 1 with up to 48
+ * channels AND cout = 2 with up to 32) = three bf16 planes per operand, hi + mid + lo == the fp32 value, x.w summed from the six
+ * products hh, hm, mh, mm, hl, lh in fp32 (the convention of ccvpe_upconv3x3_s3_f32; W is split inside the kernel from the same
+ * fp32 pack) — fp32-class error, not bit-identical to split = 0; the fp32 path's tails.  Any other value, and any (split, cout,
+ * c0) the library has no kernel for, is refused with CCVPE_EINVAL before anything is launched.
  * ----------------------------------------------------------------------------------------- */
 typedef struct ccvpe_tail_desc {
   const void* x;
