@@ -164,6 +164,25 @@ def bn_act_bwd(x, dv, mean, var, gamma, beta, eps, act, gate=None, dmean=None, d
     return dx, dgamma, dbeta
 
 
+def bn_act_bwd_frozen(x, dv, mean, var, gamma, beta, eps, act, gate=None, dmean=None, dc_scale=None):
+    """Backward of ops.bn_act with FROZEN statistics (mean / var constants, e.g. the running buffers): returns
+    (dx, dgamma, dbeta) from one pass over (x, dv) (ccvpe_bn_act_bwd_frozen_f32).  gate / dmean [B,C] fold the SE branches in."""
+    lib = _lib.load()
+    for t, nm in ((x, "x"), (dv, "dv"), (mean, "mean"), (var, "var"), (gamma, "gamma"), (beta, "beta"), (gate, "gate"),
+                  (dmean, "dmean"), (dc_scale, "dc_scale")):
+        ops._chk(t, nm)
+    b, rps, c = _bc(x)
+    dx = torch.empty_like(x)
+    both = torch.empty((2, c), device=x.device, dtype=torch.float32)       # dbeta, dgamma adjacent: one merge launch
+    dbeta, dgamma = both[0], both[1]
+    scratch = torch.empty((2 * c * b * lib.ccvpe_bn_bwd_nblk(rps),), device=x.device, dtype=torch.float32)
+    check(lib.ccvpe_bn_act_bwd_frozen_f32(ops._ptr(x), ops._ptr(dv), ops._ptr(mean), ops._ptr(var), ops._ptr(gamma),
+                                          ops._ptr(beta), ops._ptr(gate), ops._ptr(dmean), ops._ptr(dc_scale), float(eps), act,
+                                          ops._ptr(dx), ops._ptr(dgamma), ops._ptr(dbeta), ops._ptr(scratch), b, rps, c,
+                                          ops._stream()), "ccvpe_bn_act_bwd_frozen_f32")
+    return dx, dgamma, dbeta
+
+
 def se_dgate_partials(x, dv, mean, var, gamma, beta, eps, act):
     lib = _lib.load()
     for t, nm in ((x, "x"), (dv, "dv")):

@@ -405,6 +405,95 @@ __global__ __launch_bounds__(256) void se_bn_finish_kernel(const float* __restri
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Frozen BatchNorm (mean / var are the running statistics: constants of the step, not functions of x).  The statistics-
+// correction terms of the backward vanish,
+//     dx = gamma*istd*g ;  dbeta = sum g ;  dgamma = sum g*xhat,
+// so dx no longer waits for the finished sums and the reduce / apply pair collapses into ONE streaming pass: x and dv are
+// read once, dx is written, and the per-workgroup [dbeta | dgamma] partials are accumulated on the way (the same partial
+// layout as bn_bwd_reduce_kernel: launch_sum_parts finishes them in fixed order, no atomics).
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void bn_bwd_frozen_kernel(const BnBwdParams p, float* __restrict__ dx,
+                                                            float* __restrict__ part /*[B*nblk][2][C]*/) {
+  extern __shared__ __attribute__((aligned(16))) float red[];   // [P][cgx][2] float4
+  const int b = blockIdx.y;
+  const int cg4 = p.C >> 2;
+  const int cgx = cg4 < 256 ? cg4 : 256;
+  const int P = 256 / cgx;
+  const int tid = threadIdx.x;
+  const int cgl = tid % cgx, pl = tid / cgx;
+  const int r0 = blockIdx.x * p.rows_per_block;
+  const int r1 = min(r0 + p.rows_per_block, p.rows_per_sample);
+  const float dcs = p.dcs ? p.dcs[b] : 1.0f;
+  float* out = part + ((size_t)b * p.nblk + blockIdx.x) * 2 * p.C;
+  for (int cc = 0; cc < cg4; cc += cgx) {
+    const int cg = cc + cgl;
+    f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = {0.f, 0.f, 0.f, 0.f};
+    if (pl < P && cg < cg4) {
+      const int c = cg * 4;
+      const f32x4 mu = *reinterpret_cast<const f32x4*>(p.mean + c);
+      const f32x4 vv = *reinterpret_cast<const f32x4*>(p.var + c);
+      const f32x4 ga = *reinterpret_cast<const f32x4*>(p.gamma + c);
+      const f32x4 be = *reinterpret_cast<const f32x4*>(p.beta + c);
+      f32x4 istd;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) istd[j] = 1.0f / sqrtf(vv[j] + p.eps);
+      const f32x4 one4 = {1.f, 1.f, 1.f, 1.f}, zero4 = {0.f, 0.f, 0.f, 0.f};
+      const f32x4 gatev = p.gate ? *reinterpret_cast<const f32x4*>(p.gate + (size_t)b * p.C + c) : one4;
+      const f32x4 dmeanv = p.dmean ? *reinterpret_cast<const f32x4*>(p.dmean + (size_t)b * p.C + c) : zero4;
+      const size_t base = ((size_t)b * p.rows_per_sample) * p.C + c;
+      const float* __restrict__ xb = p.x + base;
+      const float* __restrict__ dvb = p.dv + base;
+      float* __restrict__ dxb = dx + base;
+      const f32x4 k = ga * istd;
+      auto rows = [&](auto act_tag) {
+        constexpr int ACT = decltype(act_tag)::value;
+        int r = r0 + pl;
+        for (; r + P < r1; r += 2 * P) {             // two rows per trip: four loads in flight
+          const f32x4 xa = *reinterpret_cast<const f32x4*>(xb + (size_t)r * p.C);
+          const f32x4 da = *reinterpret_cast<const f32x4*>(dvb + (size_t)r * p.C);
+          const f32x4 xc = *reinterpret_cast<const f32x4*>(xb + (size_t)(r + P) * p.C);
+          const f32x4 dc = *reinterpret_cast<const f32x4*>(dvb + (size_t)(r + P) * p.C);
+          f32x4 g, xh, g2, xh2;
+          bn_bwd_g_t<ACT>(xa, da, gatev, dmeanv, mu, istd, ga, be, dcs, g, xh);
+          bn_bwd_g_t<ACT>(xc, dc, gatev, dmeanv, mu, istd, ga, be, dcs, g2, xh2);
+          *reinterpret_cast<f32x4*>(dxb + (size_t)r * p.C) = k * g;
+          *reinterpret_cast<f32x4*>(dxb + (size_t)(r + P) * p.C) = k * g2;
+          s0 += g;
+          s1 += g * xh;
+          s0 += g2;
+          s1 += g2 * xh2;
+        }
+        if (r < r1) {
+          f32x4 g, xh;
+          bn_bwd_g_t<ACT>(*reinterpret_cast<const f32x4*>(xb + (size_t)r * p.C), *reinterpret_cast<const f32x4*>(dvb + (size_t)r * p.C),
+                          gatev, dmeanv, mu, istd, ga, be, dcs, g, xh);
+          *reinterpret_cast<f32x4*>(dxb + (size_t)r * p.C) = k * g;
+          s0 += g;
+          s1 += g * xh;
+        }
+      };
+      CCVPE_BN_ACT_DISPATCH(p.act, rows);
+    }
+    f32x4* red4 = reinterpret_cast<f32x4*>(red);
+    if (pl < P) {
+      red4[(pl * cgx + cgl) * 2] = s0;
+      red4[(pl * cgx + cgl) * 2 + 1] = s1;
+    }
+    __syncthreads();
+    if (pl == 0 && cg < cg4) {
+      f32x4 t0 = red4[cgl * 2], t1 = red4[cgl * 2 + 1];
+      for (int q = 1; q < P; ++q) {
+        t0 += red4[(q * cgx + cgl) * 2];
+        t1 += red4[(q * cgx + cgl) * 2 + 1];
+      }
+      *reinterpret_cast<f32x4*>(out + cg * 4) = t0;
+      *reinterpret_cast<f32x4*>(out + p.C + cg * 4) = t1;
+    }
+    __syncthreads();
+  }
+}
+
 // dx = dy where y > 0 else 0   (ReLU between the two convs of double_conv, models.py:45)
 __global__ __launch_bounds__(256) void relu_bwd_kernel(const float* __restrict__ y, const float* __restrict__ dy,
                                                        float* __restrict__ dx, long n4) {
@@ -467,6 +556,28 @@ extern "C" int ccvpe_bn_act_bwd_f32(const float* x, const float* dv, const float
   hipLaunchKernelGGL(bn_bwd_apply_kernel, grid, dim3(256), 0, st, p, dbeta, dgamma,
                      1.0f / ((float)batch * (float)rows_per_sample), dx);
   return check_launch("bn_act_bwd");
+}
+
+extern "C" int ccvpe_bn_act_bwd_frozen_f32(const float* x, const float* dv, const float* mean, const float* var,
+                                           const float* gamma, const float* beta, const float* gate, const float* dmean,
+                                           const float* dc_scale, float eps, int act, float* dx, float* dgamma, float* dbeta,
+                                           float* scratch, int batch, int rows_per_sample, int channels, void* stream) {
+  BnBwdParams p;
+  const int rc = fill_bn_params(p, x, dv, mean, var, gamma, beta, gate, dmean, dc_scale, eps, act, batch, rows_per_sample,
+                                channels);
+  if (rc) return rc;
+  if (!dx || !dgamma || !dbeta || !scratch) return fail(CCVPE_EINVAL, "bn_act_bwd_frozen: null output");
+  if (!aligned16(dx) || !aligned16(scratch)) return fail(CCVPE_EINVAL, "bn_act_bwd_frozen: pointers must be 16-byte aligned");
+  const int cg4 = channels / 4, cgx = cg4 < 256 ? cg4 : 256, P = 256 / cgx;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(bn_bwd_frozen_kernel, dim3(p.nblk, batch), dim3(256), (size_t)P * cgx * 2 * 16, st, p, dx, scratch);
+  if (dgamma == dbeta + channels) {   // adjacent outputs (what the host side allocates): the partial rows are [dbeta | dgamma] too
+    launch_sum_parts(scratch, p.nblk * batch, 2L * channels, 2 * channels, dbeta, st);
+  } else {
+    launch_sum_parts(scratch, p.nblk * batch, 2L * channels, channels, dbeta, st);
+    launch_sum_parts(scratch + channels, p.nblk * batch, 2L * channels, channels, dgamma, st);
+  }
+  return check_launch("bn_act_bwd_frozen");
 }
 
 extern "C" int ccvpe_se_bn_bwd_reduce_f32(const float* x, const float* dv, const float* mean, const float* var,

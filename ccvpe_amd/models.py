@@ -686,12 +686,27 @@ class _CVMBase(nn.Module):
     drop_connect_rate = 0.2          # efficientnet_pytorch/utils.py:639 (GlobalParams default)
     BN_MOMENTUM = 0.01               # model.py:52
 
+    bn_frozen = False                # freeze_batchnorm(): train mode normalises with the running statistics
+
+    def freeze_batchnorm(self, mode=True):
+        """Fine-tuning with BatchNorm held at its running statistics: the reference's `model.train()` followed by `m.eval()`
+        on every BatchNorm2d (the BatchNorm layers here are plain holders, so that idiom has nothing to act on).  Affects
+        train mode only and survives train() / eval() toggles: the train-mode forward normalises with running_mean /
+        running_var and writes neither them nor num_batches_tracked; the backward treats them as constants (one streaming
+        pass per BatchNorm, ccvpe_bn_act_bwd_frozen_f32); BatchNorm weight and bias still get gradients and drop_connect is
+        still governed by drop_connect_rate.  eval() is unchanged.  freeze_batchnorm(False) restores batch statistics."""
+        self.bn_frozen = bool(mode)
+        return self
+
     def forward(self, grd, sat, drop_masks=None):
         """Eval mode: the full inference path.  Train mode (self.training): the reference's training semantics
         (batch-statistic BatchNorm with running-stat updates, drop_connect); when autograd is enabled the returned
         tensors carry a graph whose backward runs the HIP backward kernels (ccvpe_amd/train.py) and fills the
         parameters' .grad — there is deliberately no eager fallback.  drop_masks: optional {(encoder prefix, block):
-        [B] 0/1 tensor} to inject the drop_connect draws (parity tests); None draws them like utils.py:145-150."""
+        [B] 0/1 tensor} to inject the drop_connect draws (parity tests); None draws them like utils.py:145-150.
+        After freeze_batchnorm() the train-mode BatchNorms use their running statistics and leave them untouched.  Eval mode
+        never carries a graph, so the reference's "`model.eval()` + backward" (gradients through the inference arithmetic)
+        is `train()` + `freeze_batchnorm()` + `drop_connect_rate = 0` here."""
         if self.training and self.precision != "fp32":
             raise NotImplementedError("ccvpe_amd: train mode is fp32 only")
         if not (grd.is_cuda and sat.is_cuda):

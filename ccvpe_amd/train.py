@@ -3,7 +3,8 @@
 Reference behaviour being reproduced: `model.train()` + `loss.backward()` on CVM_VIGOR / CVM_VIGOR_ori_prior /
 CVM_KITTI (train_VIGOR.py:193-229, train_KITTI.py): BatchNorm with batch statistics and running-stat
 updates (efficientnet_pytorch/model.py:63,73,87,182,210), drop_connect (utils.py:129-154), gradients for
-every parameter the forward touches.
+every parameter the forward touches.  With model.bn_frozen (models.freeze_batchnorm) every BatchNorm normalises with its
+running statistics instead — the reference's `model.train()` with each BatchNorm2d in `.eval()` — and leaves its buffers alone.
 
 Design: ONE torch.autograd.Function for the whole model.  forward() runs the HIP kernels and keeps a tape of
 the tensors the backward needs (raw conv outputs + batch statistics, not the normalised tensors: BN +
@@ -42,8 +43,14 @@ def _round_up(v, m):
 # forward
 # ------------------------------------------------------------------------------------------------------
 def _bn(model, live, name, x_raw, act, residual=None, dc=None, want_se=False):
-    mean, var = ops.bn_stats(x_raw, live[name + ".running_mean"], live[name + ".running_var"], model.BN_MOMENTUM)
-    model._nbt_pending.append(live[name + ".num_batches_tracked"])      # bumped once per forward with one foreach add
+    if model.bn_frozen:
+        # frozen BatchNorm (models.freeze_batchnorm): the running statistics normalise, as in the reference's BatchNorm2d.eval()
+        # inside model.train(); no statistics pass, no running-stat / num_batches_tracked update.  The tape keeps the live
+        # buffers themselves: nothing writes them between this forward and its backward.
+        mean, var = live[name + ".running_mean"], live[name + ".running_var"]
+    else:
+        mean, var = ops.bn_stats(x_raw, live[name + ".running_mean"], live[name + ".running_var"], model.BN_MOMENTUM)
+        model._nbt_pending.append(live[name + ".num_batches_tracked"])      # bumped once per forward with one foreach add
     out = ops.bn_act(x_raw, mean, var, live[name + ".weight"].detach(), live[name + ".bias"].detach(), BN_EPS, act,
                      residual=residual, dc_scale=dc, want_se=want_se)
     return out, mean, var
@@ -52,7 +59,7 @@ def _bn(model, live, name, x_raw, act, residual=None, dc=None, want_se=False):
 def encoder_forward(model, e, live, prefix, img, circular, multiscale, drop_masks, rec):
     """EfficientNet.extract_features[_multiscale] with self.training == True (model.py:278-326).
     Returns (features [B,h,w,1280], per-block outputs, tape or None)."""
-    tape = {"blocks": []} if rec else None
+    tape = {"blocks": [], "frozen": bool(model.bn_frozen)} if rec else None
     stem_raw = ops.stem_conv_raw(img, e.stem_w, circular)
     x, m, v = _bn(model, live, prefix + "._bn0", stem_raw, ops.ACT_SWISH)
     if rec:
@@ -150,8 +157,9 @@ def forward_train(model, grd, sat, drop_masks=None, rec=False):
     main.wait_stream(side)
     if side is not main:
         gdesc.record_stream(main)                 # (read by the matching kernels on the main stream)
-    model._stats_epoch = getattr(model, "_stats_epoch", 0) + 1      # the folded (eval) pack is stale now
-    torch._foreach_add_(model._nbt_pending, 1)                      # num_batches_tracked += 1 for all 98 BatchNorms
+    if model._nbt_pending:                                              # (empty with frozen BatchNorm: no buffer was written)
+        model._stats_epoch = getattr(model, "_stats_epoch", 0) + 1      # the folded (eval) pack is stale now
+        torch._foreach_add_(model._nbt_pending, 1)                      # num_batches_tracked += 1 for all 98 BatchNorms
     model._nbt_pending = []
     sdesc = ops.conv_igemm(svol, 1280, pk.sd_w, pk.sd_n, batch=batch, in_h=svol.shape[1], in_w=svol.shape[2],
                            kh=2, kw=2, stride=2, shift=pk.sd_bias)
@@ -231,9 +239,9 @@ def _p(live, name):
     return live[name].detach()
 
 
-def _bn_bwd(live, name, grads, x_raw, dv, mean, var, act, **kw):
-    dx, dgamma, dbeta = bw.bn_act_bwd(x_raw, dv, mean, var, _p(live, name + ".weight"), _p(live, name + ".bias"), BN_EPS,
-                                      act, **kw)
+def _bn_bwd(live, name, grads, x_raw, dv, mean, var, act, frozen=False, **kw):
+    fn = bw.bn_act_bwd_frozen if frozen else bw.bn_act_bwd        # frozen: mean / var are constants, one pass (csrc/train_bwd.hip)
+    dx, dgamma, dbeta = fn(x_raw, dv, mean, var, _p(live, name + ".weight"), _p(live, name + ".bias"), BN_EPS, act, **kw)
     grads[name + ".weight"] = dgamma
     grads[name + ".bias"] = dbeta
     return dx
@@ -243,8 +251,9 @@ def encoder_backward(e, live, prefix, tape, dfeat, dfeats, circular, grads, bwd=
     """dfeat: gradient w.r.t. the 1280-channel output; dfeats {block index: gradient w.r.t. that block's output}.
     bwd: {parameter name: weight in the backward layout} from the train pack (models._pack_backward)."""
     bwd = bwd or {}
+    frozen = tape.get("frozen", False)         # BatchNorm ran on the running statistics in this tape's forward
     x_last, h_raw, m, v = tape["head"]
-    dh = _bn_bwd(live, prefix + "._bn1", grads, h_raw, dfeat, m, v, ops.ACT_SWISH)
+    dh = _bn_bwd(live, prefix + "._bn1", grads, h_raw, dfeat, m, v, ops.ACT_SWISH, frozen=frozen)
     grads[prefix + "._conv_head.weight"] = bw.conv_wgrad(x_last, dh, 1280, 1, 1, 1, 0)
     dx = bw.conv1x1_dgrad(dh, _p(live, prefix + "._conv_head.weight"), wp=bwd.get(prefix + "._conv_head.weight"))
     for i in reversed(range(len(e.blocks))):
@@ -254,26 +263,37 @@ def encoder_backward(e, live, prefix, tape, dfeat, dfeats, circular, grads, bwd=
             bw.add_cols(dfeats[i], 0, blk.cout, dx)
         h, w = s["hw"]
         # project conv + bn2 (+ residual, drop_connect)
-        dp = _bn_bwd(live, bp + "._bn2", grads, s["p_raw"], dx, s["m2"], s["v2"], ops.ACT_NONE, dc_scale=s["dc"])
+        dp = _bn_bwd(live, bp + "._bn2", grads, s["p_raw"], dx, s["m2"], s["v2"], ops.ACT_NONE, frozen=frozen,
+                     dc_scale=s["dc"])
         grads[bp + "._project_conv.weight"] = bw.conv1x1_wgrad_gated(s["u"], s["gate"], dp, blk.cout)
         dv = bw.conv1x1_dgrad(dp, _p(live, bp + "._project_conv.weight"), wp=bwd.get(bp + "._project_conv.weight"))
         # squeeze-excite
         g1, b1 = _p(live, bp + "._bn1.weight"), _p(live, bp + "._bn1.bias")
         # BN1 + SE backward in two passes over (u_raw, dv): five per-(sample, channel) sums first (A[0] = the gate gradient),
         # the small SE backward on them, then dbeta / dgamma finished from the sums and dx written (csrc/train_bwd.hip)
-        sums = bw.se_bn_bwd_reduce(s["u_raw"], dv, s["m1"], s["v1"], g1, b1, BN_EPS, ops.ACT_SWISH)
         ho, wo = s["u_raw"].shape[1], s["u_raw"].shape[2]
-        dmean, dw1, db1, dw2, db2 = bw.se_bwd(s["part"], ho * wo, sums[0].unsqueeze(1), blk.se_w1, blk.se_b1, blk.se_w2, blk.se_b2)
+        if frozen:
+            # frozen statistics: dx needs no finished sums, so the gate gradient is the only thing the SE backward waits for
+            # (se_dgate partials), and one pass then writes dx with the dbeta / dgamma partials
+            dgate = bw.se_dgate_partials(s["u_raw"], dv, s["m1"], s["v1"], g1, b1, BN_EPS, ops.ACT_SWISH)
+        else:
+            sums = bw.se_bn_bwd_reduce(s["u_raw"], dv, s["m1"], s["v1"], g1, b1, BN_EPS, ops.ACT_SWISH)
+            dgate = sums[0].unsqueeze(1)
+        dmean, dw1, db1, dw2, db2 = bw.se_bwd(s["part"], ho * wo, dgate, blk.se_w1, blk.se_b1, blk.se_w2, blk.se_b2)
         grads[bp + "._se_reduce.weight"], grads[bp + "._se_reduce.bias"] = dw1, db1
         grads[bp + "._se_expand.weight"], grads[bp + "._se_expand.bias"] = dw2, db2
         # depthwise conv + bn1
-        du, dg1, db1n = bw.se_bn_bwd_apply(s["u_raw"], dv, s["m1"], s["v1"], g1, b1, BN_EPS, ops.ACT_SWISH, s["gate"], dmean, sums)
+        if frozen:
+            du, dg1, db1n = bw.bn_act_bwd_frozen(s["u_raw"], dv, s["m1"], s["v1"], g1, b1, BN_EPS, ops.ACT_SWISH, gate=s["gate"],
+                                                 dmean=dmean)
+        else:
+            du, dg1, db1n = bw.se_bn_bwd_apply(s["u_raw"], dv, s["m1"], s["v1"], g1, b1, BN_EPS, ops.ACT_SWISH, s["gate"], dmean, sums)
         grads[bp + "._bn1.weight"], grads[bp + "._bn1.bias"] = dg1, db1n
         grads[bp + "._depthwise_conv.weight"] = bw.dwconv_wgrad(s["t"], du, blk.k, blk.s, circular).t()
         dt = bw.dwconv_dgrad(du, blk.w_dw, h, w, blk.k, blk.s, circular, w_flipped=bwd.get(bp + "._depthwise_conv.weight"))
         # expand conv + bn0
         if blk.expand:
-            de = _bn_bwd(live, bp + "._bn0", grads, s["e_raw"], dt, s["m0"], s["v0"], ops.ACT_SWISH)
+            de = _bn_bwd(live, bp + "._bn0", grads, s["e_raw"], dt, s["m0"], s["v0"], ops.ACT_SWISH, frozen=frozen)
             grads[bp + "._expand_conv.weight"] = bw.conv_wgrad(s["x_in"], de, blk.mid, 1, 1, 1, 0)
             dxin = bw.conv1x1_dgrad(de, _p(live, bp + "._expand_conv.weight"), wp=bwd.get(bp + "._expand_conv.weight"))
         else:
@@ -282,7 +302,7 @@ def encoder_backward(e, live, prefix, tape, dfeat, dfeats, circular, grads, bwd=
             bw.add_cols(dx, 0, blk.cin, dxin)
         dx = dxin
     img, stem_raw, m, v = tape["stem"]
-    ds = _bn_bwd(live, prefix + "._bn0", grads, stem_raw, dx, m, v, ops.ACT_SWISH)
+    ds = _bn_bwd(live, prefix + "._bn0", grads, stem_raw, dx, m, v, ops.ACT_SWISH, frozen=frozen)
     grads[prefix + "._conv_stem.weight"] = bw.stem_conv_wgrad(img, ds, circular).permute(3, 2, 0, 1)
 
 

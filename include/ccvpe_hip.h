@@ -485,6 +485,14 @@ int ccvpe_bn_act_bwd_f32(const float* x, const float* dv, const float* mean, con
                          const float* beta, const float* gate, const float* dmean, const float* dc_scale, float eps,
                          int act, float* dx, float* dgamma, float* dbeta, float* scratch, int batch,
                          int rows_per_sample, int channels, void* stream);
+/* Frozen BatchNorm (mean / var are constants of the step: the running statistics): the same arguments, preconditions and
+ * scratch size as ccvpe_bn_act_bwd_f32, without the statistics-correction terms: g = (dv*gate + dmean) * dc_scale[b] * act'(z),
+ * dx = gamma*istd*g, dbeta = sum g, dgamma = sum g*xhat.  One pass over (x, dv): dx and the per-workgroup partial sums come
+ * out of the same kernel; the partials are merged in fixed order (no atomics). */
+int ccvpe_bn_act_bwd_frozen_f32(const float* x, const float* dv, const float* mean, const float* var, const float* gamma,
+                                const float* beta, const float* gate, const float* dmean, const float* dc_scale, float eps,
+                                int act, float* dx, float* dgamma, float* dbeta, float* scratch, int batch,
+                                int rows_per_sample, int channels, void* stream);
 /* BatchNorm + squeeze-excite backward in two passes over (x, dv) instead of three (csrc/train_bwd.hip): the reduce pass
  * returns A [5][batch][channels] = per-(sample, channel) sums of (dv*u, dv*a', a', dv*a'*xhat, a'*xhat); A[0] is the SE gate
  * gradient (feed it to ccvpe_se_bwd_f32 as a one-row partial), and the apply call finishes dbeta / dgamma from A, gate and

@@ -2,7 +2,11 @@
 B = 64 VIGOR training step (aerial: 512 x 512 image; `ground` = 320 x 640), fp32:
     python tools/bn_probe.py [reps] [aerial|ground]
 per layer shape: the plain backward (reduce + apply), the SE form's reduce and apply, and a torch `add(x, dv, out=dx)` as the
-yardstick of a 2-read-1-write streaming pass on the same tensors.  Buffers rotate so that every launch reads cold HBM."""
+yardstick of a 2-read-1-write streaming pass on the same tensors.  Buffers rotate so that every launch reads cold HBM.
+Frozen BatchNorm (models.freeze_batchnorm): the one-pass ccvpe_bn_act_bwd_frozen_f32 (`frozen`, against `bwd`) and, for the
+SE form, se_dgate partials + the frozen pass with gate / dmean (`dgate` + `frozen-se`, against `se-reduce` + `apply`).
+These are isolated-kernel times on cold buffers (event-timed, launch overhead included): they rank the kernels against the
+streaming yardstick; what the step gains is measured on the step (tools/gpu/frozen_bn_step.py)."""
 import os
 import sys
 
@@ -57,10 +61,17 @@ for (nm, c, rows, cnt, se) in layers:
     a = bw.se_bn_bwd_reduce(xs[0], dvs[0], mean, var, gamma, beta, 1e-3, ops.ACT_SWISH)
     t_red = timed([lambda i=i: bw.se_bn_bwd_reduce(xs[i], dvs[i], mean, var, gamma, beta, 1e-3, ops.ACT_SWISH) for i in range(nbuf)])
     t_app = timed([lambda i=i: bw.se_bn_bwd_apply(xs[i], dvs[i], mean, var, gamma, beta, 1e-3, ops.ACT_SWISH, gate, dmean, a) for i in range(nbuf)])
-    gbs = lambda passes, us: passes * nbytes / us * 1e-6 / 1e3       # noqa: E731  TB/s
+    t_frz = timed([lambda i=i: bw.bn_act_bwd_frozen(xs[i], dvs[i], mean, var, gamma, beta, 1e-3, ops.ACT_SWISH) for i in range(nbuf)])
+    t_dgt = timed([lambda i=i: bw.se_dgate_partials(xs[i], dvs[i], mean, var, gamma, beta, 1e-3, ops.ACT_SWISH) for i in range(nbuf)])
+    t_fse = timed([lambda i=i: bw.bn_act_bwd_frozen(xs[i], dvs[i], mean, var, gamma, beta, 1e-3, ops.ACT_SWISH, gate=gate, dmean=dmean)
+                   for i in range(nbuf)])
+    gbs = lambda passes, us: passes * nbytes / us * 1e-6       # noqa: E731  TB/s (bytes per microsecond = MB/s)
     print("%-18s C %4d px %6d (%6.0f MB) x%d  add %7.1f us (%.2f TB/s)  bwd %7.1f (%.2f over 5 passes)  se-reduce %7.1f (%.2f)  apply %7.1f (%.2f)"
           % (nm, c, rows, nbytes / 1e6, cnt, t_add, gbs(3, t_add), t_plain, gbs(5, t_plain), t_red, gbs(2, t_red), t_app, gbs(3, t_app)), flush=True)
-    for k, v in (("add", t_add), ("bwd", t_plain), ("se_reduce", t_red), ("apply", t_app)):
+    print("%-18s frozen %7.1f us (%.2f TB/s over 3 passes; bwd / frozen %.2f)  dgate %7.1f (%.2f)  frozen-se %7.1f (%.2f; (se-reduce + apply) / (dgate + frozen-se) %.2f)"
+          % ("", t_frz, gbs(3, t_frz), t_plain / t_frz, t_dgt, gbs(2, t_dgt), t_fse, gbs(3, t_fse), (t_red + t_app) / (t_dgt + t_fse)), flush=True)
+    for k, v in (("add", t_add), ("bwd", t_plain), ("se_reduce", t_red), ("apply", t_app), ("frozen", t_frz), ("dgate", t_dgt),
+                 ("frozen_se", t_fse)):
         tot[k] = tot.get(k, 0.0) + v * cnt
     del xs, dvs, out
     torch.cuda.empty_cache()
