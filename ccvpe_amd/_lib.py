@@ -169,6 +169,10 @@ PROTOTYPES = {
     "ccvpe_adam_chunk_elems": (c_int, []),
     "ccvpe_adam_hyper_floats": (c_int, []),
     "ccvpe_adam_step_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float, c_void_p]),
+    "ccvpe_adam_device_layout": (c_int, [c_int]),
+    "ccvpe_grad_sqnorm_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_float, c_void_p, c_void_p]),
+    "ccvpe_adam_prepare_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_float, c_void_p, c_void_p]),
+    "ccvpe_adam_update_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float, c_void_p, c_void_p]),
     "ccvpe_preprocess_u8_f32": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p,
                                         c_void_p, c_int, c_int, c_int, c_int, ctypes.POINTER(c_float), ctypes.POINTER(c_float),
                                         c_void_p]),

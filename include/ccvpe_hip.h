@@ -603,6 +603,34 @@ int ccvpe_adam_step_f32(const void* table, const float* hyper, const int* chunk_
                         float grad_scale, void* stream);
 
 /* -------------------------------------------------------------------------------------------
+ * Device-side optimizer (csrc/optim.hip): Adam / AdamW whose per-step numbers live in device memory, so a step needs no
+ * host arithmetic, no upload and no read-back and captures into a hipGraph.  Same table and chunk maps as
+ * ccvpe_adam_step_f32.  ccvpe_adam_device_layout(what): 0 = floats per derived hyper row, 1 = doubles per constant row,
+ * 2 = floats in the scalar block.
+ *   ccvpe_grad_sqnorm_f32: partials[c] = sum over chunk c of (grad_scale * g)^2 in a fixed order; a NULL grad gives 0.
+ *   ccvpe_adam_prepare_f32 (one workgroup):
+ *     scalars (total_norm, clip_coef, finite, skipped_steps): total_norm = sqrt(sum of the n_partials partials), the L2 norm
+ *     of all gradients as torch.nn.utils.clip_grad_norm_ forms it; clip_coef = min(1, max_norm / (total_norm + 1e-6)), torch's
+ *     formula (1 when max_norm <= 0); finite = 0 and skipped_steps += 1 when the norm is inf / NaN - the step is then SKIPPED
+ *     (torch would scale by NaN).  n_partials == 0: no norm pass, total_norm 0, clip_coef 1, finite 1.
+ *     Unless skipped, for every tensor with a non-NULL grad: steps[t] += 1 (fp32 counts, as torch's capturable optimizers keep
+ *     them) and hyper[t] = (lr / (1 - beta1^t), beta1, beta2, 1 - beta1, 1 - beta2, eps, sqrt(1 - beta2^t), l2, decay, 0)
+ *     formed in double from consts[t] = (lr, beta1, beta2, eps, weight_decay, decoupled), as torch.optim.Adam does with
+ *     Python floats: l2 = weight_decay and decay = 1 (torch.optim.Adam: g += weight_decay * p) when decoupled == 0,
+ *     l2 = 0 and decay = 1 - lr * weight_decay (torch.optim.AdamW: p *= 1 - lr * weight_decay) otherwise.
+ *   ccvpe_adam_update_f32: ccvpe_adam_step_f32's arithmetic on rows of that layout with g scaled by
+ *     grad_scale * clip_coef; g += l2 * p before the moments, p *= decay before the update; returns early for every tensor
+ *     when finite == 0 (parameters, both moments and the step counts stay untouched).
+ * ----------------------------------------------------------------------------------------- */
+int ccvpe_adam_device_layout(int what);
+int ccvpe_grad_sqnorm_f32(const void* table, const int* chunk_tensor, const int* chunk_off, int n_chunks, float grad_scale,
+                          float* partials, void* stream);
+int ccvpe_adam_prepare_f32(const void* table, const double* consts, float* steps, float* hyper, int n_tensors,
+                           const float* partials, int n_partials, float max_norm, float* scalars, void* stream);
+int ccvpe_adam_update_f32(const void* table, const float* hyper, const int* chunk_tensor, const int* chunk_off, int n_chunks,
+                          float grad_scale, const float* scalars, void* stream);
+
+/* -------------------------------------------------------------------------------------------
  * Input pipeline after JPEG decoding (csrc/preprocess.hip): transforms.Resize on a PIL image
  * (= Pillow's antialiased 8-bit BILINEAR resampler, reproduced bit for bit), ToTensor, Normalize
  * (train_VIGOR.py:57-70), torch.roll along W (datasets.py:112-121) and the FoV crop (train_VIGOR.py:177-178).

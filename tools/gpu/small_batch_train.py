@@ -1,5 +1,8 @@
-"""Small-batch training step, eager vs GraphedTrainStep (forward + losses + backward in one hipGraph, eager Adam):
-    python tools/gpu/small_batch_train.py [batch ...]"""
+"""Small-batch training step, three ways: eager; GraphedTrainStep (forward + losses + backward in one hipGraph) followed by the
+eager host-path Adam; GraphedTrainStep with the capturable device-side Adam inside (the whole iteration replayed):
+    python tools/gpu/small_batch_train.py [batch ...]
+CCVPE_SBT_OPT=1 additionally times the optimizer alone on the full parameter set: the one host-path launch against the
+device path's two launches and its three with the global-norm pass."""
 import os
 import sys
 import time
@@ -59,7 +62,20 @@ for batch in [int(a) for a in sys.argv[1:]] or [8]:
         step()
         opt.step()
     ms_g = timed(graphed)
-    print("B = %d: eager %.2f ms/step (%.0f pairs/s), graphed %.2f ms/step (%.0f pairs/s), loss %.4g" %
-          (batch, ms_e, batch / ms_e * 1e3, ms_g, batch / ms_g * 1e3, float(step.loss)))
+    del net, opt, step
+    torch.cuda.empty_cache()
+    net, loss_fn = build(batch)
+    opt = optim.Adam(net.parameters(), lr=1e-4, capturable=True)
+    step = graph.GraphedTrainStep(loss_fn, net, optimizer=opt)
+    ms_o = timed(step)
+    print("B = %d: eager %.2f ms/step (%.0f pairs/s), graphed + host Adam %.2f ms/step (%.0f pairs/s), "
+          "graphed with Adam inside %.2f ms/step (%.0f pairs/s), loss %.4g" %
+          (batch, ms_e, batch / ms_e * 1e3, ms_g, batch / ms_g * 1e3, ms_o, batch / ms_o * 1e3, float(step.loss)))
+    if os.environ.get("CCVPE_SBT_OPT") == "1":           # the optimizer alone, on the gradients the last replay left
+        host = optim.Adam(net.parameters(), lr=1e-4)
+        dev3 = optim.Adam(net.parameters(), lr=1e-4, max_grad_norm=1e30)
+        print("    optimizer alone, %d tensors: host path (1 launch) %.3f ms, device path (2 launches) %.3f ms, "
+              "with the norm pass (3 launches) %.3f ms" % (len(step.params), timed(host.step, 50), timed(opt.step, 50), timed(dev3.step, 50)))
+        del host, dev3
     del net, opt, step
     torch.cuda.empty_cache()
