@@ -9,11 +9,12 @@ namespace ccvpe {
 // NW = waves per workgroup (4 or 8).  The 8-wave form (512 threads, 2x the pixel tile) stages the same W
 // tile per K-stage for twice the MFMAs: the ablation (tools/ablation) attributes 11 % of the 4-wave
 // kernel's time to W staging, 2 % to barriers, 5 % to LDS fragment reads (MFMA-only ceiling 140 TF).
-// DMA = W tile staged by LDS-DMA (global_load_lds_dwordx4: no VGPR round trip, no ds_write, no wait before
+// The W tile is staged by LDS-DMA (global_load_lds_dwordx4: no VGPR round trip, no ds_write, no wait before
 // the LDS store).  The DMA writes lane-linear (base + lane*16 B), so the W stage is an UNPADDED [BN][64 B]
 // image and the bank-conflict fix is an XOR swizzle of the 16-byte piece index, applied to the per-lane
 // SOURCE address and to the fragment read: slot(r, c) = 4r + (c ^ perm[(r>>2)&3]), perm = (0,2,3,1)
-// (conflict-free for the four ds_read_b128 lane groups).  Needs Npad % BN == 0 (no row guard possible).
+// (conflict-free for the four ds_read_b128 lane groups).  Needs Npad % BN == 0 (no row guard possible): pick_cfg
+// only returns tiles whose width divides Npad, and launch3x3 refuses anything else.
 #ifdef CCVPE_ABLATE   // diagnostics build only (make EXTRA=-DCCVPE_ABLATE): A/B switches read from the environment at load
 // CCVPE_CONV3_TPS=1: one tap per stage instead of a row of taps; CCVPE_CONV3_WREG=1: fp32 3x3 convolutions through
 // conv3x3_wreg_kernel (W fragments straight from L2); CCVPE_CONV3_NW8=0: never the 8-wave form of the 128-column tile
@@ -25,13 +26,13 @@ constexpr bool g_conv3_nw8 = true;
 constexpr int g_conv3_tps = 3;
 #endif
 
-// TPS = taps per stage.  TPS = 1: one (16-channel chunk, tap) per stage.  TPS = 3 (W by LDS-DMA only): a stage is one ROW of
+// TPS = taps per stage.  TPS = 1: one (16-channel chunk, tap) per stage.  TPS = 3: a stage is one ROW of
 // taps (ky; kx = 0..2) of a chunk — three W panels land per stage, the fragments of tap kx+1 are read from LDS while the
 // MFMAs of tap kx run (two fragment register sets), and the closing barrier, the DMA's vmcnt(0) and the exposed first LDS
 // round trip are paid once per 240 matrix instructions instead of once per 80.
-template <typename T, int MT, int NT, int WN, int NW, bool DMA, int TPS>
+template <typename T, int MT, int NT, int WN, int NW, int TPS>
 struct Conv3Geom {
-  static constexpr int BLD = DMA ? 16 : LDS_LD;
+  static constexpr int BLD = 16;                   // floats per W stage row: the DMA's unpadded 64 bytes
   static constexpr int WM = NW / WN;
   static constexpr int BM = 16 * MT * WM;
   static constexpr int BN = 16 * NT * WN;
@@ -40,24 +41,20 @@ struct Conv3Geom {
   // Halo pixel rows of 64 bytes (no padding) in 24 slots per halo row, the 16-byte piece index XOR-ed by
   // ((column >> 2) & 1) << 1: conflict-free ds_read_b128 fragments (tools/lds_layout.py) at 7 % more LDS instead of 2-way
   // conflicts on every read; with 24 = 0 mod 8 slots per row the swizzle term depends on (lane, kx) only -> three per-lane
-  // address registers, rows and ky by immediate offsets.  (HSW = false is the round-3 layout: 18 slots of 80 bytes.)
-  // (the 8-wave fp32 form without W DMA — a fallback for column counts that are not a tile multiple — lives under a 128-VGPR
-  // cap and spills with the three extra address registers: it keeps the round-3 layout)
-  static constexpr bool HSW = !(NW == 8 && sizeof(T) == 4 && !DMA);
-  static constexpr int HCP = HSW ? 24 : 18;
-  static constexpr int HLD = HSW ? 16 : LDS_LD;
+  // address registers, rows and ky by immediate offsets.
+  static constexpr int HCP = 24;
+  static constexpr int HLD = 16;
   static constexpr int HS_FLOATS = (TH + 2) * HCP * HLD;
   static constexpr int BS_FLOATS = 2 * TPS * BN * BLD;
   static constexpr int LDS_BYTES = (HS_FLOATS + BS_FLOATS) * 4;
 };
 
-template <typename T, int MT, int NT, int WN, int NW, bool DMA, int TPS>
+template <typename T, int MT, int NT, int WN, int NW, int TPS>
 __global__ __launch_bounds__(64 * NW, (NW == 8 && sizeof(T) == 4) ? 4 : 2) void conv3x3_kernel(const IgemmParams p) {
-  static_assert(TPS == 1 || (TPS == 3 && DMA), "a row of taps per stage needs the DMA W path");
-  using G = Conv3Geom<T, MT, NT, WN, NW, DMA, TPS>;
+  static_assert(TPS == 1 || TPS == 3, "a stage is one tap or one row of taps");
+  using G = Conv3Geom<T, MT, NT, WN, NW, TPS>;
   constexpr int BLD = G::BLD;                      // floats per W stage row
   constexpr int NTHR = 64 * NW;
-  constexpr int RPP = NTHR / 4;                    // staged rows per pass
   constexpr int E = ElemTraits<T>::E;
   constexpr int SK = 4 * E;                        // channels per chunk: 16 (fp32) or 32 (bf16)
   constexpr int WM = NW / WN;
@@ -68,14 +65,12 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 && sizeof(T) == 4) ? 4 : 2) void 
   constexpr int HC = 18;                           // halo columns
   constexpr int HPX = HR * HC;
   constexpr int H_IT = (HPX * 4 + NTHR - 1) / NTHR;  // float4 loads per thread per chunk (halo)
-  constexpr int B_IT = (BN + RPP - 1) / RPP;
   constexpr int NG = 9 / TPS;                      // stages per chunk
-  constexpr bool HSW = G::HSW;
   constexpr int HCP = G::HCP, HLD = G::HLD;
 
   // halo is single-buffered (one extra barrier per chunk) to keep LDS small -> 2-4 blocks/CU
   extern __shared__ __attribute__((aligned(16))) float c3_sm[];
-  float* Hs = c3_sm;                               // [HPX][LDS_LD]
+  float* Hs = c3_sm;                               // [HR][HCP][HLD]
   float* Bs = c3_sm + G::HS_FLOATS;                // [2][TPS][BN][BLD]
 
   const int tid = threadIdx.x;
@@ -111,16 +106,15 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 && sizeof(T) == 4) ? 4 : 2) void 
     if (px < HPX) {
       const int hy = px / HC, hx = px - hy * HC;
       const int iy = y0 - 1 + hy, ix = x0 - 1 + hx;
-      h_off[it] = (hy * HCP + hx) * HLD + (HSW ? (sub ^ (((hx >> 2) & 1) << 1)) : sub) * 4;
+      h_off[it] = (hy * HCP + hx) * HLD + (sub ^ (((hx >> 2) & 1) << 1)) * 4;
       h_pix[it] = ((unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W) ? (b * p.H + iy) * p.W + ix : -1;
     } else {
       h_off[it] = -1;
       h_pix[it] = -1;
     }
   }
-  const int srow = tid >> 2, ssub = tid & 3;
 
-  f32x4 h_reg[H_IT], b_reg[B_IT];
+  f32x4 h_reg[H_IT];
   int h_chunk = 0;                         // chunk held in h_reg (workgroup-uniform: lives in a scalar register)
   const int ld0s = sgpr(p.ld0), ld1s = sgpr(p.ld1);
 
@@ -148,9 +142,9 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 && sizeof(T) == 4) ? 4 : 2) void 
   // the stage's K offset is added to the SCALAR base, so requesting a panel costs no vector ALU work at all — with the
   // address rebuilt per instruction (64-bit multiply-adds) the requests of a stage were a ~500-cycle burst of VALU work in
   // front of every MFMA block (ablation: 136 TF without the W requests, 118 with them, the same with their wait removed).
-  constexpr int NSLOT = DMA ? (BN / 16 + NW - 1) / NW : 1;
+  constexpr int NSLOT = (BN / 16 + NW - 1) / NW;
   unsigned wvoff[NSLOT];
-  if constexpr (DMA) {
+  {
     const int rl = lane >> 2;
     const int c = (lane & 3) ^ w_swz(rl);
 #pragma unroll
@@ -161,44 +155,25 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 && sizeof(T) == 4) ? 4 : 2) void 
   }
   const unsigned bs_lds = (unsigned)(uintptr_t)(__attribute__((address_space(3))) float*)Bs;
   auto load_w = [&](int chunk, int tg, int dbuf) {   // the TPS taps tg*TPS .. of `chunk` -> Bs[dbuf][0..TPS)
-    if constexpr (DMA) {
 #pragma unroll
-      for (int t = 0; t < TPS; ++t) {
-        const char* sbase = reinterpret_cast<const char*>(wp) + ((size_t)(tg * TPS + t) * ctot + (size_t)chunk * SK) * sizeof(T);
+    for (int t = 0; t < TPS; ++t) {
+      const char* sbase = reinterpret_cast<const char*>(wp) + ((size_t)(tg * TPS + t) * ctot + (size_t)chunk * SK) * sizeof(T);
 #pragma unroll
-        for (int q = 0; q < NSLOT; ++q) {
-          const int g = wave + NW * q;
-          if (g < BN / 16) {
-            // Inline assembly: for the builtin the compiler waits vmcnt(0) in front of every later LDS read it cannot prove
-            // disjoint from the DMA's target, which forces the request to the END of a stage.  Written this way the panels
-            // of the NEXT stage are requested at the START of the stage; dma_wait() below is the matching vmcnt(0).
-            const unsigned lds = __builtin_amdgcn_readfirstlane(bs_lds + (unsigned)(((dbuf * TPS + t) * BN + g * 16) * BLD * 4));
-            asm volatile("s_mov_b32 m0, %0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(lds), "v"(wvoff[q]), "s"(sbase)
-                         : "memory", "m0");
-          }
+      for (int q = 0; q < NSLOT; ++q) {
+        const int g = wave + NW * q;
+        if (g < BN / 16) {
+          // Inline assembly: for the builtin the compiler waits vmcnt(0) in front of every later LDS read it cannot prove
+          // disjoint from the DMA's target, which forces the request to the END of a stage.  Written this way the panels
+          // of the NEXT stage are requested at the START of the stage; dma_wait() below is the matching vmcnt(0).
+          const unsigned lds = __builtin_amdgcn_readfirstlane(bs_lds + (unsigned)(((dbuf * TPS + t) * BN + g * 16) * BLD * 4));
+          asm volatile("s_mov_b32 m0, %0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(lds), "v"(wvoff[q]), "s"(sbase)
+                       : "memory", "m0");
         }
-      }
-    } else {
-      const int ch = chunk * SK + ssub * E;
-      const int kcol = ch < ctot ? tg * ctot + ch : 0;         // beyond the channel range the halo piece is zero anyway
-#pragma unroll
-      for (int it = 0; it < B_IT; ++it) {
-        const int nr = min(n0 + srow + RPP * it, p.Npad - 1);
-        b_reg[it] = *reinterpret_cast<const f32x4*>(wp + (size_t)nr * p.Kpad + kcol);
-      }
-    }
-  };
-  auto store_w = [&](int buf) {
-    if constexpr (!DMA) {
-#pragma unroll
-      for (int it = 0; it < B_IT; ++it) {
-        const int nrow = srow + RPP * it;
-        if (nrow < BN) *reinterpret_cast<f32x4*>(&Bs[(buf * BN + nrow) * BLD + ssub * 4]) = b_reg[it];
       }
     }
   };
   auto dma_wait = [&]() {                  // the W panels requested by load_w have landed in LDS (this wave's share)
-    if constexpr (DMA) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   };
 
   f32x4 acc[MT][NT];
@@ -208,19 +183,17 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 && sizeof(T) == 4) ? 4 : 2) void 
     for (int j = 0; j < NT; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
   const int frow = lane & 15;
-  const int fk = (lane >> 4) * 4;
-  const int bcol = DMA ? (((lane >> 4) ^ w_swz(frow)) * 4) : fk;
+  const int bcol = ((lane >> 4) ^ w_swz(frow)) * 4;
   int acol[3];                                     // per-lane float offset of the A fragment for kx = 0..2 (row 0 of this wave)
 #pragma unroll
   for (int kx = 0; kx < 3; ++kx) {
     const int hx = frow + kx;
-    acol[kx] = (wm * MT * HCP + hx) * HLD + (HSW ? (((lane >> 4) ^ (((hx >> 2) & 1) << 1)) * 4) : fk);
+    acol[kx] = (wm * MT * HCP + hx) * HLD + ((lane >> 4) ^ (((hx >> 2) & 1) << 1)) * 4;
   }
 
   load_halo(0);
   load_w(0, 0, 0);
   store_halo();
-  store_w(0);
   dma_wait();
   __syncthreads();
 
@@ -246,9 +219,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 && sizeof(T) == 4) ? 4 : 2) void 
       if constexpr (TPS == 3) ab = acol[t];
       else ab = kx == 0 ? acol[0] : (kx == 1 ? acol[1] : acol[2]);
 #pragma unroll
-      for (int i = 0; i < MT; ++i)
-        if constexpr (HSW) a[i] = *reinterpret_cast<const f32x4*>(Hs + ab + (i + ky) * HCP * HLD);
-        else a[i] = *reinterpret_cast<const f32x4*>(Hs + (((wm * MT + i) + ky) * HC + frow + kx) * LDS_LD + fk);
+      for (int i = 0; i < MT; ++i) a[i] = *reinterpret_cast<const f32x4*>(Hs + ab + (i + ky) * HCP * HLD);
 #pragma unroll
       for (int j = 0; j < NT; ++j)
         w_[j] = *reinterpret_cast<const f32x4*>(&Bs[((((s & 1) * TPS + t) * BN) + (wn * NT + j) * 16 + frow) * BLD + bcol]);
@@ -286,7 +257,6 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 && sizeof(T) == 4) ? 4 : 2) void 
     // keep the closing barrier (and the vmcnt(0) the DMA needs in front of it) BELOW the matrix work: the scheduler moves
     // s_barrier freely among MFMAs and had put it after the first one
     __builtin_amdgcn_sched_barrier(0);
-    if (more) store_w((s + 1) & 1);
     if (!(abl & 128)) dma_wait();
     if (!(abl & 16)) __syncthreads();
     if (tg == NG - 1 && more && !(abl & 64)) {   // chunk boundary: every wave is done reading the halo -> overwrite it
@@ -582,7 +552,7 @@ static int launch3x3_nw(const IgemmParams& p0, int batch, int variant, hipStream
     }
   }
 #endif
-  static bool attr_set[3] = {false, false, false};      // per (T, tile) instantiation of this launcher: one flag per kernel variant
+  static bool attr_set[2] = {false, false};             // per (T, tile) instantiation of this launcher: one flag per kernel variant
   auto go = [&](int slot, void (*kern)(const IgemmParams), int lds) -> int {
     if (!attr_set[slot] && lds > 48 * 1024) {
       hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
@@ -592,18 +562,12 @@ static int launch3x3_nw(const IgemmParams& p0, int batch, int variant, hipStream
     hipLaunchKernelGGL(kern, dim3(p.tiles_total), dim3(64 * NW), lds, stream, p);
     return CCVPE_OK;
   };
-  const bool dma = (variant >> 4) & 1;                  // conv3x3_variant(): the form is decided there, only instantiated here
-  const int tps = variant >> 8;
-  int rc;
-  if (dma) {
-    if constexpr (conv3_row_stage<T, NT, WN, NW>()) {
-      if (tps == 3) rc = go(0, conv3x3_kernel<T, MT, NT, WN, NW, true, 3>, Conv3Geom<T, MT, NT, WN, NW, true, 3>::LDS_BYTES);
-      else rc = go(1, conv3x3_kernel<T, MT, NT, WN, NW, true, 1>, Conv3Geom<T, MT, NT, WN, NW, true, 1>::LDS_BYTES);
-    } else {
-      rc = go(1, conv3x3_kernel<T, MT, NT, WN, NW, true, 1>, Conv3Geom<T, MT, NT, WN, NW, true, 1>::LDS_BYTES);
-    }
+  int rc;                                               // conv3x3_variant(): the form is decided there, only instantiated here
+  if constexpr (conv3_row_stage<T, NT, WN, NW>()) {
+    if ((variant >> 8) == 3) rc = go(0, conv3x3_kernel<T, MT, NT, WN, NW, 3>, Conv3Geom<T, MT, NT, WN, NW, 3>::LDS_BYTES);
+    else rc = go(1, conv3x3_kernel<T, MT, NT, WN, NW, 1>, Conv3Geom<T, MT, NT, WN, NW, 1>::LDS_BYTES);
   } else {
-    rc = go(2, conv3x3_kernel<T, MT, NT, WN, NW, false, 1>, Conv3Geom<T, MT, NT, WN, NW, false, 1>::LDS_BYTES);
+    rc = go(1, conv3x3_kernel<T, MT, NT, WN, NW, 1>, Conv3Geom<T, MT, NT, WN, NW, 1>::LDS_BYTES);
   }
   if (rc) return rc;
   return check_launch("conv3x3_kernel");
@@ -612,31 +576,34 @@ static int launch3x3_nw(const IgemmParams& p0, int batch, int variant, hipStream
 template <typename T, int MT, int NT, int WN>
 static int launch3x3(const IgemmParams& p0, int batch, hipStream_t stream) {
   const int variant = conv3x3_variant<T, MT, NT, WN>(p0, batch);
+  // the DMA has no row guard; pick_cfg never returns such a tile (tests/test_abi.py), so this is a caller's error
+  if (!((variant >> 4) & 1))
+    return fail(CCVPE_EINVAL, "conv3x3: tile <%d,%d,%d> is %d columns wide, which does not divide Npad = %d (W is staged by LDS-DMA)",
+                MT, NT, WN, 16 * NT * WN, p0.Npad);
   if constexpr (conv3_has_nw8<T, NT, WN>()) {
     if ((variant & 15) == 8) return launch3x3_nw<T, MT, NT, WN, 8>(p0, batch, variant, stream);
   }
   return launch3x3_nw<T, MT, NT, WN, 4>(p0, batch, variant, stream);
 }
 
+// ONE switch over the tile table for both questions about a row <mt, nt, wn> of it: launch it (conv3x3_dispatch), or report the
+// form that launch would take without launching (conv3x3_variant_query: NW | DMA << 4 | TPS << 8, 0 for no such tile; host only)
+template <typename T>
+static int conv3x3_tile(const IgemmParams& p, int batch, int mt, int nt, int wn, bool query, hipStream_t stream) {
+#define CCVPE_CASE(MT_, NT_, WN_) \
+  if (mt == MT_ && nt == NT_ && wn == WN_) \
+    return query ? conv3x3_variant<T, MT_, NT_, WN_>(p, batch) : launch3x3<T, MT_, NT_, WN_>(p, batch, stream);
+  CCVPE_TILES(CCVPE_CASE)
+#undef CCVPE_CASE
+  return query ? 0 : fail(CCVPE_EINVAL, "conv3x3: no tile <%d,%d,%d>", mt, nt, wn);
+}
 template <typename T>
 int conv3x3_dispatch(const IgemmParams& p, int batch, int mt, int nt, int wn, hipStream_t stream) {
-#define CCVPE_CASE(MT_, NT_, WN_) \
-  if (mt == MT_ && nt == NT_ && wn == WN_) return launch3x3<T, MT_, NT_, WN_>(p, batch, stream);
-  CCVPE_CASE(4, 5, 2) CCVPE_CASE(4, 4, 2) CCVPE_CASE(4, 3, 2) CCVPE_CASE(4, 2, 2) CCVPE_CASE(4, 1, 2)
-  CCVPE_CASE(4, 5, 1) CCVPE_CASE(4, 3, 1) CCVPE_CASE(4, 1, 1) CCVPE_CASE(2, 7, 1)
-#undef CCVPE_CASE
-  return fail(CCVPE_EINVAL, "conv3x3: no tile <%d,%d,%d>", mt, nt, wn);
+  return conv3x3_tile<T>(p, batch, mt, nt, wn, false, stream);
 }
-
-// the form conv3x3_dispatch would launch for this tile (NW | DMA << 4 | TPS << 8), 0 for a tile it does not instantiate; host only
 template <typename T>
 int conv3x3_variant_query(const IgemmParams& p, int batch, int mt, int nt, int wn) {
-#define CCVPE_CASE(MT_, NT_, WN_) \
-  if (mt == MT_ && nt == NT_ && wn == WN_) return conv3x3_variant<T, MT_, NT_, WN_>(p, batch);
-  CCVPE_CASE(4, 5, 2) CCVPE_CASE(4, 4, 2) CCVPE_CASE(4, 3, 2) CCVPE_CASE(4, 2, 2) CCVPE_CASE(4, 1, 2)
-  CCVPE_CASE(4, 5, 1) CCVPE_CASE(4, 3, 1) CCVPE_CASE(4, 1, 1) CCVPE_CASE(2, 7, 1)
-#undef CCVPE_CASE
-  return 0;
+  return conv3x3_tile<T>(p, batch, mt, nt, wn, true, nullptr);
 }
 
 }  // namespace ccvpe

@@ -243,13 +243,18 @@ __device__ __forceinline__ void store4(const IgemmParams& p, f32x4 v, int n, siz
 // W-stage swizzle of the LDS-DMA kernels (conv3x3_impl.h): slot(r, c) = 4r + (c ^ perm[(r>>2)&3]), perm = (0,2,3,1)
 __device__ __forceinline__ int w_swz(int r) { return (0x1320 >> (((r >> 2) & 3) * 4)) & 3; }
 
+// The <MT, NT, WN> tile table, written ONCE: kCfgs and every full-table switch (conv_igemm.hip, conv3x3_impl.h, upconv_impl.h)
+// are generated from this list.  X(MT, NT, WN) per row.
+#define CCVPE_TILES(X)                                                            \
+  X(4, 5, 2) X(4, 4, 2) X(4, 3, 2) X(4, 2, 2) X(4, 1, 2) /* BN 160,128,96,64,32  BM 128 */ \
+  X(4, 5, 1) X(4, 3, 1) X(4, 1, 1)                       /* BN 80,48,16          BM 256 */ \
+  X(2, 7, 1)                                             /* BN 112               BM 128 */
+
 // Pick the N tile that wastes the fewest MFMA columns, then the widest.
 struct TileCfg { int mt, nt, wn; };
-static const TileCfg kCfgs[] = {
-    {4, 5, 2}, {4, 4, 2}, {4, 3, 2}, {4, 2, 2}, {4, 1, 2},  // BN 160,128,96,64,32  BM 128
-    {4, 5, 1}, {4, 3, 1}, {4, 1, 1},                        // BN 80,48,16          BM 256
-    {2, 7, 1},                                              // BN 112               BM 128
-};
+#define CCVPE_TILE_ROW(MT_, NT_, WN_) {MT_, NT_, WN_},
+static const TileCfg kCfgs[] = {CCVPE_TILES(CCVPE_TILE_ROW)};
+#undef CCVPE_TILE_ROW
 
 static int pick_cfg(int npad16) {
   int best = 0;

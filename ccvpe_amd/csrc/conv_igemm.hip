@@ -290,23 +290,14 @@ static int splitk_slices(int tiles, int stages) {
 }
 
 template <typename T, int MT, int NT, int WN>
-static int launch(const IgemmParams& p0, hipStream_t stream, float* scratch = nullptr, long* want_floats = nullptr) {
-  constexpr int WM = 4 / WN;
-  constexpr int BM = 16 * MT * WM;
-  constexpr int BN = 16 * NT * WN;
+static int launch(const IgemmParams& p0, hipStream_t stream, float* scratch) {
+  constexpr int BM = 16 * MT * (4 / WN), BN = 16 * NT * WN;
   IgemmParams p = p0;
-  const int tiles_m = (p.M + BM - 1) / BM;
   p.tiles_n = (p.Npad + BN - 1) / BN;
-  p.tiles_total = tiles_m * p.tiles_n;
-  p.ksplit = 1;
-  p.sps = p.stages;
-  p.partial = nullptr;
-  const int S = splitk_slices(p.tiles_total, p.stages);
-  if (want_floats) {                       // planning call: report the scratch a split-K run needs, launch nothing
-    *want_floats = S > 1 ? (long)S * p.M * p.Npad : 0;
-    return CCVPE_OK;
-  }
-  if (scratch && S > 1) {
+  p.tiles_total = ((p.M + BM - 1) / BM) * p.tiles_n;
+  p.ksplit = 1; p.sps = p.stages; p.partial = nullptr;
+  const int S = scratch ? splitk_slices(p.tiles_total, p.stages) : 1;      // (splitk_want: the same question at planning time)
+  if (S > 1) {
     p.sps = (p.stages + S - 1) / S;
     p.ksplit = (p.stages + p.sps - 1) / p.sps;
     p.partial = scratch;
@@ -319,6 +310,14 @@ static int launch(const IgemmParams& p0, hipStream_t stream, float* scratch = nu
   return check_launch("igemm_kernel");
 }
 
+template <typename T>
+static int igemm_dispatch(const IgemmParams& p, TileCfg c, hipStream_t stream, float* scratch) {
+#define CCVPE_CASE(MT_, NT_, WN_) \
+  if (c.mt == MT_ && c.nt == NT_ && c.wn == WN_) return launch<T, MT_, NT_, WN_>(p, stream, scratch);
+  CCVPE_TILES(CCVPE_CASE)
+#undef CCVPE_CASE
+  return fail(CCVPE_EINVAL, "conv_igemm: no tile config");
+}
 
 }  // namespace ccvpe
 
@@ -345,15 +344,9 @@ extern "C" int ccvpe_set_pw_ring_kernels(int on) {
   return prev;
 }
 
-// route (optional): filled with the kernel family + tile the dispatcher picks for `d` (CCVPE_ROUTE_* | MT << 8 | NT << 12 |
-// WN << 16) and NOTHING is launched — ccvpe_conv_igemm_route(); tests and bench.py's launch recorder read it instead of
-// mirroring the dispatch rules in Python
-// the next level's one-hypothesis matching fused into a 3x3 layer's epilogue (ccvpe_conv3x3_match1_bf16)
-struct MatchFuse { const float* g; int ldg, L, off; float* scores; bool query; };
-
+// Validates `d` and fills the kernels' parameter block; every entry point below starts here.
 template <typename T>
-static int conv_igemm_any(const ccvpe_conv_desc* d, void* stream, int out_f32, float* scratch = nullptr,
-                          long* want_floats = nullptr, int* route = nullptr, const MatchFuse* mf = nullptr, int* variant = nullptr) {
+static int fill_params(const ccvpe_conv_desc* d, int out_f32, IgemmParams& p) {
   constexpr int E = ElemTraits<T>::E;
   constexpr int SK = 4 * E;
   if (!d) return fail(CCVPE_EINVAL, "conv_igemm: null desc");
@@ -369,7 +362,7 @@ static int conv_igemm_any(const ccvpe_conv_desc* d, void* stream, int out_f32, f
   if (d->stride < 1 || d->kh < 1 || d->kw < 1) return fail(CCVPE_EINVAL, "conv_igemm: bad kernel/stride");
   if (d->act == CCVPE_ACT_RELU_MASK && (!d->residual || d->out_mode != CCVPE_OUT_NHWC))
     return fail(CCVPE_EINVAL, "conv_igemm: CCVPE_ACT_RELU_MASK needs the ReLU output in `residual` and an NHWC store");
-  IgemmParams p{};
+  p = IgemmParams{};
   p.src0 = d->src0; p.src1 = d->src1; p.gate = d->gate; p.w = d->w;
   p.scale = d->scale; p.shift = d->shift; p.residual = d->residual; p.dst = d->dst;
   p.out_f32 = out_f32;
@@ -393,152 +386,157 @@ static int conv_igemm_any(const ccvpe_conv_desc* d, void* stream, int out_f32, f
   if (M <= 0 || M > 0x7fffffffL) return fail(CCVPE_EINVAL, "conv_igemm: bad M");
   if ((long)d->batch * d->in_h * d->in_w > 0x7fffffffL) return fail(CCVPE_EINVAL, "conv_igemm: too many pixels");
   p.M = (int)M;
-  p.tiles_n = p.tiles_total = p.tiles_x = p.tiles_y = 0;
-  hipStream_t st = (hipStream_t)stream;
+  return CCVPE_OK;
+}
+
+// ---- the route: which kernel family and tile serve a layer.  pick_route() alone knows the order of the families; the launch,
+// ccvpe_conv_igemm_route / ccvpe_conv3x3_variant (tests and bench.py's launch recorder read them instead of mirroring the rules
+// in Python) and the split-K planner go through it or through its predicates
+struct ConvRoute { int fam, mt, nt, wn; };      // fam: CCVPE_ROUTE_*; the ABI's encoding is fam | mt << 8 | nt << 12 | wn << 16
+
+static bool is3x3(const ccvpe_conv_desc* d) {
+  return d->kh == 3 && d->kw == 3 && d->stride == 1 && d->pad == 1 && d->out_mode == CCVPE_OUT_NHWC && !d->gate;
+}
+// pointwise convs (1x1, stride 1, one source, plain NHWC store) take the deep-stage kernels; the residual / bf16 rows
+// they touch with 16-byte accesses must be 16-byte aligned along the channel axis
+template <typename T>
+static bool is_pw(const ccvpe_conv_desc* d, const IgemmParams& p) {
+  const int esz = (int)sizeof(T);
+  const bool out32 = esz == 4 || p.out_f32;
+  return g_use_pw && d->kh == 1 && d->kw == 1 && d->stride == 1 && d->pad == 0 && d->c1 == 0 &&
+         d->act != CCVPE_ACT_RELU && d->act != CCVPE_ACT_RELU_MASK &&
+         d->n > 48 &&      // narrow outputs (N <= 48: 16-48 column tiles) stay with the generic kernel
+         d->out_mode == CCVPE_OUT_NHWC && (d->ldd * (out32 ? 4 : 2)) % 16 == 0 &&
+         (!d->residual || (d->ldres * esz) % 16 == 0);
+}
+// the tile the pointwise kernels run where the table says `c` (nt == 0: none, `c` is no wider than 48 columns).  The 256 x 80 tile
+// needs more than 256 VGPRs there (staging registers live across the epilogue): N = 65..80 layers take the 128 x 96 tile.
+static TileCfg pw_tile(int mt, int nt, int wn) {
+  if (16 * nt * wn <= 48) return TileCfg{0, 0, 0};
+  if (mt == 4 && nt == 5 && wn == 1) return TileCfg{4, 3, 2};
+  return TileCfg{mt, nt, wn};
+}
+
+// one-pass route of a validated layer (a split-K run is the generic kernel by definition)
+template <typename T>
+static ConvRoute pick_route(const ccvpe_conv_desc* d, const IgemmParams& p) {
+  const int esz = (int)sizeof(T);
+  // N <= 48, K <= 256 (fp32: 144) projections on large planes: weights (x SE gate) in registers; tile fields = N / 16, K bytes / 64
+  if (pwn_supported(p, d->batch, esz)) return ConvRoute{CCVPE_ROUTE_PWN, p.Npad / 16, (p.Kpad * esz) / 64, 0};
   const TileCfg c = kCfgs[pick_cfg(p.Npad)];
-  const bool is3x3 = d->kh == 3 && d->kw == 3 && d->stride == 1 && d->pad == 1 &&
-                     d->out_mode == CCVPE_OUT_NHWC && !d->gate;
-  if (mf) {
-    if constexpr (sizeof(T) == 2) {
-      const bool ok = is3x3 && g_use_narrow && c3n_match_supported(p, d->batch, mf->L);
-      if (mf->query) return ok ? 1 : 0;
-      if (!ok) return fail(CCVPE_EINVAL, "conv3x3_match1: this layer / shape is not served (ask ccvpe_conv3x3_match1_ok first)");
-      return c3n_match_dispatch(p, d->batch, mf->g, mf->ldg, mf->L, mf->off, mf->scores, st);
-    } else {
-      return mf->query ? 0 : fail(CCVPE_EINVAL, "conv3x3_match1: bf16 storage only");
-    }
+  if (is3x3(d)) {
+    if (esz == 2 && g_use_narrow && c3n_supported(p, d->batch)) return ConvRoute{CCVPE_ROUTE_C3N, c.mt, c.nt, c.wn};
+    return ConvRoute{CCVPE_ROUTE_CONV3X3, c.mt, c.nt, c.wn};
   }
+  const TileCfg t = pw_tile(c.mt, c.nt, c.wn);
+  if (t.nt && is_pw<T>(d, p))
+    return ConvRoute{pw2_supported<T>(p, t.mt, t.nt, t.wn) ? CCVPE_ROUTE_PW_RING : CCVPE_ROUTE_PW_GEMM, t.mt, t.nt, t.wn};
+  return ConvRoute{CCVPE_ROUTE_IGEMM, c.mt, c.nt, c.wn};
+}
+
+// planning: the fp32 scratch words a split-K run needs, 0 = one pass.  Two bf16 "do not split" rules, else the generic kernel's
+// own answer (also for a layer pwn_supported() would serve: planning does not consult that kernel)
+template <typename T>
+static long splitk_want(const ccvpe_conv_desc* d, const IgemmParams& p) {
+  const TileCfg c = kCfgs[pick_cfg(p.Npad)];
   // bf16 3x3 on images >= 16 columns wide with at least 128 halo tiles: the LDS-DMA 3x3 kernel UN-split beats the split-K gather
   // kernel + its second pass (tools/conv3_probe.py bf16, 16 x 16 images: B = 32 257 -> 166 us at 1344 -> 640 and 140 -> 82 us at
-  // 640 -> 640, B = 16 equal, B = 8 slower), so the planning call reports "no split" there.  fp32 keeps the split (its 3x3 kernel
-  // needs two workgroups per CU to cover its own latencies).
-  if (want_floats && sizeof(T) == 2 && is3x3 && p.W >= 16) {
+  // 640 -> 640, B = 16 equal, B = 8 slower).  fp32 keeps the split (its 3x3 kernel needs two workgroups per CU to cover its latencies)
+  if (sizeof(T) == 2 && is3x3(d) && p.W >= 16) {
     const int th = c.mt * (4 / c.wn), bn = 16 * c.nt * c.wn;
     const long tiles = (long)d->batch * ((p.H + th - 1) / th) * ((p.W + 15) / 16) * ((p.Npad + bn - 1) / bn);
-    if (tiles >= 128) {
-      *want_floats = 0;
-      return CCVPE_OK;
-    }
+    if (tiles >= 128) return 0;
   }
-  // split-K mode (planning or with scratch): everything, 3x3 included, goes through the generic gather kernel
-  const bool sk = scratch != nullptr || want_floats != nullptr;
-  if (scratch && !aligned16(scratch)) return fail(CCVPE_EINVAL, "conv_igemm: scratch must be 16-byte aligned");
-  // pointwise convs (1x1, stride 1, one source, plain NHWC store) take the deep-stage kernel; the residual / bf16 rows
-  // it touches with 16-byte accesses must be 16-byte aligned along the channel axis
-  const int esz = (int)sizeof(T);
-  const bool out32 = esz == 4 || out_f32;
-  const bool is_pw = g_use_pw && d->kh == 1 && d->kw == 1 && d->stride == 1 && d->pad == 0 && d->c1 == 0 && d->act != CCVPE_ACT_RELU &&
-                     d->act != CCVPE_ACT_RELU_MASK &&
-                     d->n > 48 &&      // narrow outputs (N <= 48: 16-48 column tiles) stay with the generic kernel
-                     d->out_mode == CCVPE_OUT_NHWC && (d->ldd * (out32 ? 4 : 2)) % 16 == 0 &&
-                     (!d->residual || (d->ldres * esz) % 16 == 0);
   // bf16 1x1 layers the ring / pointwise kernels take, with >= 200 of their tiles (B = 64: the late MBConv projections 1152 -> 192
   // / 320 at 16 x 16 and 10 x 20): one pass beats the split gather kernel + its second pass there (round 6, same-box A/B of the
   // C1 forward: 8.94 -> 8.87 ms; at B = 32 — 100-128 tiles — the split still wins: C2 5.17 vs 5.25 ms)
-  if (want_floats && !route && sizeof(T) == 2 && is_pw && 16 * c.nt * c.wn > 48) {
-    const bool rr = c.mt == 4 && c.nt == 5 && c.wn == 1;             // (re-routed to the 128 x 96 tile below)
-    const int bm = 16 * c.mt * (4 / (rr ? 2 : c.wn)), bn = 16 * (rr ? 3 : c.nt) * (rr ? 2 : c.wn);
+  const TileCfg t = pw_tile(c.mt, c.nt, c.wn);
+  if (sizeof(T) == 2 && t.nt && is_pw<T>(d, p)) {
+    const int bm = 16 * t.mt * (4 / t.wn), bn = 16 * t.nt * t.wn;
     const long tiles = (long)((p.M + bm - 1) / bm) * ((p.Npad + bn - 1) / bn);
-    if (tiles >= 200) {
-      *want_floats = 0;
-      return CCVPE_OK;
-    }
+    if (tiles >= 200) return 0;
   }
-  // the 256 x 80 tile needs more than 256 VGPRs in the persistent pointwise kernel (staging registers live across the
-  // epilogue): N = 65..80 pointwise layers take the 128 x 96 tile there
-  // projections with N <= 48 and K <= 256 (fp32: 144) on large planes: the streaming kernel with the weights (x SE gate) in registers
-  if (!scratch && !mf && pwn_supported(p, d->batch, (int)sizeof(T))) {
-    if (route) {
-      *route = CCVPE_ROUTE_PWN | ((p.Npad / 16) << 8) | (((p.Kpad * (int)sizeof(T)) / 64) << 12);
-      return CCVPE_OK;
-    }
-    if (!want_floats) return pwn_dispatch(p, d->batch, (int)sizeof(T), st);
-  }
-  if (route) {
-    const bool pw_tile = 16 * c.nt * c.wn > 48;      // (the 256 x 80 tile is re-routed to 128 x 96 below)
-    int mt = c.mt, nt = c.nt, wn = c.wn, fam = CCVPE_ROUTE_IGEMM;
-    if (is3x3 && sizeof(T) == 2 && g_use_narrow && c3n_supported(p, d->batch)) fam = CCVPE_ROUTE_C3N;
-    else if (is3x3) fam = CCVPE_ROUTE_CONV3X3;
-    else if (is_pw && pw_tile) {
-      fam = CCVPE_ROUTE_PW_GEMM;
-      if (mt == 4 && nt == 5 && wn == 1) { nt = 3; wn = 2; }
-      if (!sk && pw2_supported<T>(p, mt, nt, wn)) fam = CCVPE_ROUTE_PW_RING;
-    }
-    *route = fam | (mt << 8) | (nt << 12) | (wn << 16);
-    // the form of conv3x3_kernel behind that route (ccvpe_conv3x3_variant): the launcher's own decision, conv3x3_impl.h
-    if (variant) *variant = fam == CCVPE_ROUTE_CONV3X3 ? conv3x3_variant_query<T>(p, d->batch, mt, nt, wn) : 0;
-    return CCVPE_OK;
-  }
-  if (!sk) {
-    if constexpr (sizeof(T) == 2) {
-      if (is3x3 && g_use_narrow && c3n_supported(p, d->batch)) return c3n_dispatch(p, d->batch, st);
-    }
-    if (is3x3) return conv3x3_dispatch<T>(p, d->batch, c.mt, c.nt, c.wn, st);
-    if (is_pw && 16 * c.nt * c.wn > 48) {
-      const bool reroute = c.mt == 4 && c.nt == 5 && c.wn == 1;
-      const int mt = c.mt, nt = reroute ? 3 : c.nt, wn = reroute ? 2 : c.wn;
-      if (pw2_supported<T>(p, mt, nt, wn)) return pw2_dispatch<T>(p, mt, nt, wn, st);
-      return pw_dispatch<T>(p, mt, nt, wn, st);
-    }
-  }
-#define CCVPE_CASE(MT_, NT_, WN_) \
-  if (c.mt == MT_ && c.nt == NT_ && c.wn == WN_) return launch<T, MT_, NT_, WN_>(p, st, scratch, want_floats);
-  CCVPE_CASE(4, 5, 2) CCVPE_CASE(4, 4, 2) CCVPE_CASE(4, 3, 2) CCVPE_CASE(4, 2, 2) CCVPE_CASE(4, 1, 2)
-  CCVPE_CASE(4, 5, 1) CCVPE_CASE(4, 3, 1) CCVPE_CASE(4, 1, 1) CCVPE_CASE(2, 7, 1)
-#undef CCVPE_CASE
-  return fail(CCVPE_EINVAL, "conv_igemm: no tile config");
+  const int bm = 16 * c.mt * (4 / c.wn), bn = 16 * c.nt * c.wn;          // the generic kernel's grid: launch<T, MT, NT, WN> above
+  const int S = splitk_slices(((p.M + bm - 1) / bm) * ((p.Npad + bn - 1) / bn), p.stages);
+  return S > 1 ? (long)S * p.M * p.Npad : 0;
 }
 
+// ---- the entry points: fill_params + one of the pieces above.  conv_run with `scratch` is a split-K run: everything, 3x3
+// included, goes through the generic gather kernel
+template <typename T>
+static int conv_run(const ccvpe_conv_desc* d, int out_f32, void* stream, float* scratch = nullptr) {
+  IgemmParams p;
+  if (const int rc = fill_params<T>(d, out_f32, p)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  if (scratch && !aligned16(scratch)) return fail(CCVPE_EINVAL, "conv_igemm: scratch must be 16-byte aligned");
+  if (scratch) return igemm_dispatch<T>(p, kCfgs[pick_cfg(p.Npad)], st, scratch);
+  const ConvRoute r = pick_route<T>(d, p);
+  switch (r.fam) {
+    case CCVPE_ROUTE_PWN: return pwn_dispatch(p, d->batch, (int)sizeof(T), st);
+    case CCVPE_ROUTE_C3N: return c3n_dispatch(p, d->batch, st);
+    case CCVPE_ROUTE_CONV3X3: return conv3x3_dispatch<T>(p, d->batch, r.mt, r.nt, r.wn, st);
+    case CCVPE_ROUTE_PW_RING: return pw2_dispatch<T>(p, r.mt, r.nt, r.wn, st);
+    case CCVPE_ROUTE_PW_GEMM: return pw_dispatch<T>(p, r.mt, r.nt, r.wn, st);
+    default: return igemm_dispatch<T>(p, TileCfg{r.mt, r.nt, r.wn}, st, nullptr);
+  }
+}
+
+// the route conv_run() would take or, with `variant`, the form of conv3x3_kernel behind it (0 for another family); no launch
+template <typename T>
+static int conv_route(const ccvpe_conv_desc* d, int out_f32, bool variant) {
+  IgemmParams p;
+  if (const int rc = fill_params<T>(d, out_f32, p)) return rc;
+  const ConvRoute r = pick_route<T>(d, p);
+  if (variant) return r.fam == CCVPE_ROUTE_CONV3X3 ? conv3x3_variant_query<T>(p, d->batch, r.mt, r.nt, r.wn) : 0;
+  return r.fam | (r.mt << 8) | (r.nt << 12) | (r.wn << 16);
+}
 
 extern "C" int ccvpe_conv_igemm_splitk_floats(const ccvpe_conv_desc* d, int is_bf16) {
-  long want = 0;
-  const int rc = is_bf16 ? conv_igemm_any<bf16_t>(d, nullptr, 0, nullptr, &want)
-                         : conv_igemm_any<float>(d, nullptr, 0, nullptr, &want);
-  if (want > 0x7fffffffL) want = 0;          // would not fit the int return: do not split
-  return rc ? rc : (int)want;
+  IgemmParams p;
+  const int rc = is_bf16 ? fill_params<bf16_t>(d, 0, p) : fill_params<float>(d, 0, p);
+  const long want = rc ? rc : is_bf16 ? splitk_want<bf16_t>(d, p) : splitk_want<float>(d, p);
+  return want > 0x7fffffffL ? 0 : (int)want;      // would not fit the int return: do not split
 }
 extern "C" int ccvpe_conv_igemm_route(const ccvpe_conv_desc* d, int is_bf16, int out_f32) {
-  int route = 0;
-  const int rc = is_bf16 ? conv_igemm_any<bf16_t>(d, nullptr, out_f32 ? 1 : 0, nullptr, nullptr, &route)
-                         : conv_igemm_any<float>(d, nullptr, 1, nullptr, nullptr, &route);
-  return rc ? rc : route;
+  return is_bf16 ? conv_route<bf16_t>(d, out_f32 ? 1 : 0, false) : conv_route<float>(d, 1, false);
 }
 extern "C" int ccvpe_conv3x3_variant(const ccvpe_conv_desc* d, int is_bf16) {
-  int route = 0, variant = 0;
-  const int rc = is_bf16 ? conv_igemm_any<bf16_t>(d, nullptr, 0, nullptr, nullptr, &route, nullptr, &variant)
-                         : conv_igemm_any<float>(d, nullptr, 1, nullptr, nullptr, &route, nullptr, &variant);
-  return rc ? rc : variant;
+  return is_bf16 ? conv_route<bf16_t>(d, 0, true) : conv_route<float>(d, 1, true);
+}
+
+// the next level's one-hypothesis matching fused into a bf16 3x3 layer's epilogue (narrow_impl.h): 1 = served, 0 = not, < 0 = bad desc
+static int match1_served(const ccvpe_conv_desc* d, int out_f32, int L, IgemmParams& p) {
+  if (const int rc = fill_params<bf16_t>(d, out_f32 ? 1 : 0, p)) return rc;
+  return is3x3(d) && g_use_narrow && c3n_match_supported(p, d->batch, L) ? 1 : 0;
 }
 static int match1_offset(int n, int shift, int stride, int window_offset) {
   long o = (-((long)shift * stride + window_offset)) % n;      // match_any()'s offset (csrc/matching.hip)
   return (int)(o < 0 ? o + n : o);
 }
 extern "C" int ccvpe_conv3x3_match1_ok(const ccvpe_conv_desc* d, int out_f32, int L) {
-  MatchFuse mf{nullptr, 0, L, 0, nullptr, true};
-  const int rc = conv_igemm_any<bf16_t>(d, nullptr, out_f32 ? 1 : 0, nullptr, nullptr, nullptr, &mf);
+  IgemmParams p;
+  const int rc = match1_served(d, out_f32, L, p);
   return rc < 0 ? 0 : rc;
 }
 extern "C" int ccvpe_conv3x3_match1_bf16(const ccvpe_conv_desc* d, int out_f32, const float* g, int ldg, int L, int shift, int stride,
                                          int window_offset, float* scores, void* stream) {
   if (!d || !g || !scores) return fail(CCVPE_EINVAL, "conv3x3_match1: null pointer");
   if (L > ldg) return fail(CCVPE_EINVAL, "conv3x3_match1: L > ldg");
-  MatchFuse mf{g, ldg, L, match1_offset(d->n, shift, stride, window_offset), scores, false};
-  return conv_igemm_any<bf16_t>(d, stream, out_f32 ? 1 : 0, nullptr, nullptr, nullptr, &mf);
+  IgemmParams p;
+  const int ok = match1_served(d, out_f32, L, p);
+  if (ok < 0) return ok;
+  if (!ok) return fail(CCVPE_EINVAL, "conv3x3_match1: this layer / shape is not served (ask ccvpe_conv3x3_match1_ok first)");
+  return c3n_match_dispatch(p, d->batch, g, ldg, L, match1_offset(d->n, shift, stride, window_offset), scores, (hipStream_t)stream);
 }
 extern "C" int ccvpe_conv_igemm_splitk_bf16(const ccvpe_conv_desc* d, int out_f32, float* scratch, void* stream) {
   if (!scratch) return fail(CCVPE_EINVAL, "conv_igemm_splitk: scratch is NULL");
-  return conv_igemm_any<bf16_t>(d, stream, out_f32, scratch);
+  return conv_run<bf16_t>(d, out_f32, stream, scratch);
 }
 extern "C" int ccvpe_conv_igemm_splitk_f32(const ccvpe_conv_desc* d, float* scratch, void* stream) {
   if (!scratch) return fail(CCVPE_EINVAL, "conv_igemm_splitk: scratch is NULL");
-  return conv_igemm_any<float>(d, stream, 0, scratch);
+  return conv_run<float>(d, 0, stream, scratch);
 }
-
-extern "C" int ccvpe_conv_igemm_f32(const ccvpe_conv_desc* d, void* stream) {
-  return conv_igemm_any<float>(d, stream, 1);
-}
-
+extern "C" int ccvpe_conv_igemm_f32(const ccvpe_conv_desc* d, void* stream) { return conv_run<float>(d, 1, stream); }
 extern "C" int ccvpe_conv_igemm_bf16(const ccvpe_conv_desc* d, int out_f32, void* stream) {
-  return conv_igemm_any<bf16_t>(d, stream, out_f32 ? 1 : 0);
+  return conv_run<bf16_t>(d, out_f32 ? 1 : 0, stream);
 }
-

@@ -379,8 +379,9 @@ template <typename T>
 int pw_dispatch(const IgemmParams& p, int mt, int nt, int wn, hipStream_t stream) {
 #define CCVPE_CASE(MT_, NT_, WN_) \
   if (mt == MT_ && nt == NT_ && wn == WN_) return launch_pw<T, MT_, NT_, WN_>(p, stream);
-  // tiles wider than 48 columns only (conv_igemm_any routes N <= 48 to the generic kernel); the 256 x 80 tile is re-routed
-  // to 128 x 96 by the caller (more than 256 VGPRs with the staging registers live across the epilogue)
+  // a deliberate SUBSET of the tile table (CCVPE_TILES, conv_common.h), kept as an explicit list:
+  // tiles wider than 48 columns only (pick_route, conv_igemm.hip, routes N <= 48 to the generic kernel); the 256 x 80 tile is
+  // re-routed to 128 x 96 there (more than 256 VGPRs with the staging registers live across the epilogue)
   CCVPE_CASE(4, 5, 2) CCVPE_CASE(4, 4, 2) CCVPE_CASE(4, 3, 2) CCVPE_CASE(4, 2, 2) CCVPE_CASE(2, 7, 1)
 #undef CCVPE_CASE
   return fail(CCVPE_EINVAL, "pw_gemm: no tile <%d,%d,%d>", mt, nt, wn);

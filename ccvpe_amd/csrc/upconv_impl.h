@@ -996,8 +996,7 @@ static int upconv_any(const ccvpe_upconv_desc* d, void* stream, int* route = nul
   const TileCfg c = kCfgs[pick_cfg(p.Npad)];
 #define CCVPE_CASE(MT_, NT_, WN_) \
   if (c.mt == MT_ && c.nt == NT_ && c.wn == WN_) return launch_up<T, MT_, NT_, WN_>(p, st, route);
-  CCVPE_CASE(4, 5, 2) CCVPE_CASE(4, 4, 2) CCVPE_CASE(4, 3, 2) CCVPE_CASE(4, 2, 2) CCVPE_CASE(4, 1, 2)
-  CCVPE_CASE(4, 5, 1) CCVPE_CASE(4, 3, 1) CCVPE_CASE(4, 1, 1) CCVPE_CASE(2, 7, 1)
+  CCVPE_TILES(CCVPE_CASE)
 #undef CCVPE_CASE
   return fail(CCVPE_EINVAL, "upconv: no tile config");
 }

@@ -451,6 +451,7 @@ static int s3_run(const ccvpe_upconv_desc* d, int form, void* stream) {
   if (d->w1 == 8 && d->h1 == 8) return launch_s3<4, 5, 2, true>(p, st);
 #define CCVPE_CASE(MT_, NT_, WN_) \
   if (c.mt == MT_ && c.nt == NT_ && c.wn == WN_) return launch_s3<MT_, NT_, WN_, false>(p, st);
+  // a deliberate SUBSET of the tile table (CCVPE_TILES, conv_common.h): the rows s3_tile() accepts, kept as an explicit list
   CCVPE_CASE(4, 5, 2) CCVPE_CASE(4, 4, 2) CCVPE_CASE(4, 2, 2) CCVPE_CASE(4, 1, 2) CCVPE_CASE(4, 5, 1) CCVPE_CASE(4, 3, 1)
 #undef CCVPE_CASE
   return fail(CCVPE_EINVAL, "upconv3x3_s3: no tile config");

@@ -105,8 +105,8 @@ int ccvpe_conv_igemm_splitk_floats(const ccvpe_conv_desc* desc, int is_bf16);
 #define CCVPE_ROUTE_PWN 5     /* (ABI 7) narrow projection kernel: N <= 48, K <= 256 (fp32: <= 144), weights x SE gate in registers, waves stream 16-pixel tiles (csrc/pwn.hip); the route's MT / NT fields hold N / 16 and K bytes / 64 */
 int ccvpe_conv_igemm_route(const ccvpe_conv_desc* desc, int is_bf16, int out_f32);
 /* Which form of the 3x3 kernel runs for a `desc` that routes to CCVPE_ROUTE_CONV3X3 (storage output, no out_f32):
- * NW | DMA << 4 | TPS << 8 — waves per workgroup (4 or 8: the 8-wave form doubles the pixel tile), W tile by LDS-DMA (1) or
- * through registers (0), taps per K stage (3 = a row of taps, 1).  0 for any other route, negative = error.  Host only: the
+ * NW | DMA << 4 | TPS << 8 — waves per workgroup (4 or 8: the 8-wave form doubles the pixel tile), W tile by LDS-DMA (1 for every
+ * tile the kernel serves), taps per K stage (3 = a row of taps, 1).  0 for any other route, negative = error.  Host only: the
  * launcher's own decision (csrc/conv3x3_impl.h: conv3x3_variant), so that a test can assert the form before it launches. */
 int ccvpe_conv3x3_variant(const ccvpe_conv_desc* desc, int is_bf16);
 /* A/B switch for measurements (process-wide, default on): 0 sends the narrow bf16 decoder layers (CCVPE_ROUTE_C3N, and the

@@ -13,7 +13,8 @@ of taps or one tap per K stage) and csrc/mbconv_plane.hip (mbband_plan), and wha
 from collections import namedtuple
 
 # ------------------------------------------------------------------------------------------------------------------------------
-# conv3x3_kernel<T, MT, NT, WN, NW, DMA, TPS>.  A workgroup tile is (16 MT NW / (16 WN)) rows x 16 columns of pixels x 16 NT WN
+# conv3x3_kernel<T, MT, NT, WN, NW, TPS> (DMA below is bit 4 of ccvpe_conv3x3_variant: W staged by LDS-DMA, always set).
+# A workgroup tile is (16 MT NW / (16 WN)) rows x 16 columns of pixels x 16 NT WN
 # output channels: <4,x,2> tiles are 8 rows tall with 4 waves and 16 with 8, <4,x,1> 16 rows, <2,7,1> 8 rows.
 #
 # Every row has two sources (c1 > 0 keeps bf16 off the narrow c3n route) and K = 9 x 40: 22.5 fp32 stages of 16 channels / 11.25
@@ -67,8 +68,7 @@ CONV3X3_NW8_PAIRS = [
 ]
 
 # What the traced B = 64 steps launch, as (MT, NT, WN, NW, DMA, TPS): tests/test_abi.py asserts that the rows above select every
-# one of them.  (conv3x3_kernel<.., DMA = false, 1> is instantiated but unreachable through ccvpe_conv_igemm_*: pick_cfg always
-# returns a tile whose width divides Npad — DESIGN.md section 4 — so it has no row.)
+# one of them.  (DMA is always True: pick_cfg only returns tiles whose width divides Npad — DESIGN.md section 4.)
 CONV3X3_TRACED_F32 = [
     (4, 5, 2, 4, True, 3), (4, 4, 2, 8, True, 1), (4, 3, 2, 4, True, 3), (4, 2, 2, 4, True, 3), (4, 1, 2, 4, True, 3),
     (4, 5, 1, 4, True, 1), (4, 3, 1, 4, True, 3), (4, 1, 1, 4, True, 3), (2, 7, 1, 4, True, 3),

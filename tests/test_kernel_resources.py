@@ -1,6 +1,5 @@
 """Static guard on the compiled kernels (no GPU needed): the build records hipcc's per-kernel resource remarks in
-ccvpe_amd/csrc/<source>.res; no kernel of the library may use scratch memory (= spilled registers), with one known,
-measured exception.  This is the check that would have caught `match_bwd_kernel<20>` before its GPU run (the SLP vectoriser
+ccvpe_amd/csrc/<source>.res; no kernel of the library may use scratch memory (= spilled registers).  This is the check that would have caught `match_bwd_kernel<20>` before its GPU run (the SLP vectoriser
 spilled its per-shift arrays: 2.9 KB of scratch per lane, 5x slower — DESIGN.md §4); `tools/kres.py` prints the same numbers."""
 import glob
 import os
@@ -9,8 +8,8 @@ import re
 from ccvpe_amd import _lib
 
 CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "ccvpe_amd", "csrc")
-# mangled-name fragment -> bytes per lane allowed (the 8-wave 128-column 3x3 tile without DMA lives under a 128-VGPR cap)
-ALLOWED = {"conv3x3_kernelIfLi4ELi4ELi2ELi8ELb0ELi1E": 32}
+# mangled-name fragment -> bytes per lane allowed: nothing is
+ALLOWED = {}
 
 
 def _kernels():

@@ -45,7 +45,8 @@ def test_bf16_layouts_in_the_source_are_conflict_free():
     assert "static constexpr int LD = SWZ ? 16 : LDS_LD;" in common
     c3 = open(os.path.join(ROOT, "ccvpe_amd", "csrc", "conv3x3_impl.h")).read()
     assert "static constexpr bool SWZ = true;" in common
-    assert "static constexpr bool HSW = !(NW == 8 && sizeof(T) == 4 && !DMA);" in c3 and "static constexpr int HCP = HSW ? 24 : 18;" in c3 and "(((hx >> 2) & 1) << 1)" in c3
+    assert "static constexpr int HCP = 24;" in c3 and "static constexpr int HLD = 16;" in c3 and "(((hx >> 2) & 1) << 1)" in c3
+    assert "HSW" not in c3.split("#ifdef CCVPE_ABLATE   // the W-from-L2 experiment")[0]      # every form of conv3x3_kernel has this halo
     pw = open(os.path.join(ROOT, "ccvpe_amd", "csrc", "conv_pw_impl.h")).read()
     assert "static constexpr bool SWZ = true;" in pw and "static constexpr int LDF = SWZ ? 16 * KP : 16 * KP + 4;" in pw and "((frow >> 1) & 7)" in pw
     swz = lambda row: ((row >> 2) & 1) << 1
