@@ -9,10 +9,12 @@ the whole-model gradient test.  Each link's output gradient is the next link's r
 
 Contents: (a) float64 stage references, (b) layout adapters, (c) the Recorder, (d) Report / compare, (e) StepChecker, which
 walks a recorded step stage by stage and then checks the joins train.py assembles itself (skip gradients, dgdesc, level 1's
-cat gradient).  Besides the calls of the backward chain the Recorder wraps train.backward_train (the gradients arriving on the
+cat gradient); StepChecker.loss_link is the chain's first link: the loss value and the gradients on the nine outputs against the
+benched loss mix restated on the recorded outputs.  Besides the calls of the backward chain the Recorder wraps train.backward_train (the gradients arriving on the
 nine outputs) and bw.l2norm2_bwd (the raw orientation field, which the tape does not hold).
 """
 import math
+import time
 
 import torch
 import torch.nn.functional as F
@@ -180,6 +182,61 @@ def ref_normalize_head(raw, g_out, dtype=torch.float64):
     def fn(xi, sd):
         return {"x": F.normalize(xi["raw"], p=2, dim=1)}
     return _run(fn, {"raw": raw}, {}, {"x": g_out}, dtype)
+
+
+# The first link: the benched loss mix on the nine outputs.  Output index -> tensor name; output 1, the heat-map, is not read.
+LOSS_OUTPUTS = {0: "logits", 2: "ori", 3: "scores1", 4: "scores2", 5: "scores3", 6: "scores4", 7: "scores5", 8: "scores6"}
+LOSS_DEVICE_MIN_ELEMENTS = 4 * 1024 * 1024    # an output above this is restated where it lives (float64 tensor operations on the device)
+LOSS_CROSSCHECK = 1e-12                       # ... and a two-sample sub-batch of it both ways must agree to this
+
+
+def _loss_term(i, outs, targets, dtype, dev, need_grad, samples=None):
+    """The mix's term that reads output i — cross_entropy (0), 1e1 * orientation (2), 1e4 * infoNCE / 6 (3 .. 8), the oracle's
+    three functions — in `dtype` on `dev`, on the first `samples` samples if given.  Returns (term, its gradient on output i or
+    None).  The infoNCE mask `> 1e-2` is decided identically on a float32 label and on its float64 copy (0.01f < 0.01 <
+    nextafter(0.01f))."""
+    gt, gt_flat, gt_ori, labels = targets
+
+    def c(t):
+        return t.detach()[:samples].to(device=dev, dtype=dtype)
+    x = c(outs[i]).clone().requires_grad_(need_grad)
+    with torch.set_grad_enabled(need_grad):
+        if i == 0:
+            term = O.cross_entropy_loss(x.flatten(1), c(gt_flat).flatten(1))
+        elif i == 2:
+            term = 1e1 * O.orientation_loss(x, c(gt_ori), c(gt))
+        else:
+            term = 1e4 * O.infonce_loss(x.flatten(1), c(labels[i - 3]).flatten(1)) / 6
+    grad = torch.autograd.grad(term, x)[0].detach() if need_grad else None
+    return term.detach(), grad
+
+
+def _loss_device(t):
+    return t.device if t.numel() > LOSS_DEVICE_MIN_ELEMENTS else torch.device("cpu")
+
+
+def ref_loss_mix(outs, targets, outputs=None, dtype=torch.float64):
+    """cross_entropy + 1e4 * sum(infoNCE) / 6 + 1e1 * orientation (the benched step's loss) on the recorded outputs, and its
+    gradient on every output in `outputs` (default: all eight the mix reads).  targets = (gt, gt_flat, gt_ori, labels) as
+    targets.train_targets returns them.  The terms share no input, so each is differentiated alone; an output above
+    LOSS_DEVICE_MIN_ELEMENTS elements is restated on its own device.  An output not in `outputs` still enters the value."""
+    outputs = sorted(LOSS_OUTPUTS) if outputs is None else outputs
+    res, loss = {}, torch.zeros((), dtype=dtype)
+    for i in sorted(LOSS_OUTPUTS):
+        term, grad = _loss_term(i, outs, targets, dtype, _loss_device(outs[i]), i in outputs)
+        loss = loss + term.cpu()
+        if grad is not None:
+            res["din:" + LOSS_OUTPUTS[i]] = grad
+    res["out:loss"] = loss
+    return res
+
+
+def loss_device_crosscheck(outs, targets, i, samples=2):
+    """Output i's term and gradient on a `samples`-sample sub-batch, float64, on the CPU and on the output's device: the largest
+    difference relative to the CPU result's largest value (term, gradient)."""
+    a = _loss_term(i, outs, targets, torch.float64, torch.device("cpu"), True, samples)
+    b = _loss_term(i, outs, targets, torch.float64, outs[i].device, True, samples)
+    return tuple(float((p - q.cpu()).abs().max()) / (float(p.abs().max()) + 1e-300) for p, q in zip(a, b))
 
 
 def ref_bn_stats(raw_nchw, dtype=torch.float64):
@@ -470,6 +527,7 @@ class StepChecker(object):
         self.dg_refs, self.cat_refs = {}, {}    # level -> (fp64, fp32) din:g; branch -> (fp64, fp32) din:cat of level 1
         self.skip_refs = {}          # (branch, skip block) -> fp64 skip gradient of that decoder level
         self.stages = []
+        self.loss_left_out, self.loss_crosschecks, self.loss_seconds = [], [], 0.0   # loss_link: outputs not compared; (name, dv, dg); wall time
 
     def _both(self, fn, *args):
         return fn(*args, dtype=torch.float64), fn(*args, dtype=torch.float32)
@@ -638,6 +696,32 @@ class StepChecker(object):
             self.report.compare("catsum:1", {"din:cat": got_cat, "din:tail": got_tail}, want[0], want[1])
             self.stages.append("catsum:1")
 
+    # -- the loss -----------------------------------------------------------------------------------------------------
+    def loss_link(self, targets, loss):
+        """The first link: rec.gout, the gradients the loss kernels put on the outputs, and the loss value, against the benched
+        mix restated on the recorded outputs (ref_loss_mix).  want(("loss", i)) selects the outputs whose gradient is compared;
+        the others still enter the value and are listed in self.loss_left_out."""
+        if not self.want(("loss",)):
+            return
+        t0 = time.time()
+        rec = self.rec
+        outputs = [i for i in sorted(LOSS_OUTPUTS) if self.want(("loss", i))]
+        self.loss_left_out = [LOSS_OUTPUTS[i] for i in sorted(LOSS_OUTPUTS) if i not in outputs]
+        assert len(rec.gout) == 9 and all(rec.gout[i] is not None for i in LOSS_OUTPUTS), "an output the mix reads received no gradient"
+        assert rec.gout[1] is None or float(rec.gout[1].abs().max()) == 0.0, "a gradient arrived on the heat-map, which the mix does not read"
+        refs = (ref_loss_mix(rec.outs, targets, outputs), ref_loss_mix(rec.outs, targets, outputs, torch.float32))
+        for i in outputs:
+            if _loss_device(rec.outs[i]).type != "cpu":
+                dv, dg = loss_device_crosscheck(rec.outs, targets, i)
+                self.loss_crosschecks.append((LOSS_OUTPUTS[i], dv, dg))
+                assert dv <= LOSS_CROSSCHECK and dg <= LOSS_CROSSCHECK, \
+                    "float64 on the device and on the CPU disagree on %s: value %.2e, gradient %.2e" % (LOSS_OUTPUTS[i], dv, dg)
+        got = {"out:loss": torch.as_tensor(loss, dtype=torch.float64)}
+        for i in outputs:
+            got["din:" + LOSS_OUTPUTS[i]] = rec.gout[i].reshape(rec.outs[i].shape)
+        self._cmp("loss", got, refs)
+        self.loss_seconds = time.time() - t0
+
     # -- output heads ------------------------------------------------------------------------------------------------
     def heads(self):
         if not self.want(("heads",)):
@@ -661,7 +745,10 @@ class StepChecker(object):
             return self.rec.outs[0].reshape(self.tape["heatmap"].shape)
         return self.rec.raw_ori
 
-    def run_all(self, circular):
+    def run_all(self, circular, targets=None, loss=None):
+        """targets, loss: what the step built and returned; given, the chain starts at the loss (loss_link)."""
+        if targets is not None:
+            self.loss_link(targets, loss)
         self.encoder("grd_efficientnet", circular, self.tape["gfeat"])
         self.encoder("sat_efficientnet", False, self.tape["svol"])
         self.descriptors()

@@ -9,9 +9,11 @@ import inspect
 
 import pytest
 import torch
+import torch.nn.functional as F
 
 import stage_check as S
 from ccvpe_amd import synth
+from oracle import ccvpe_oracle as O
 
 WHOLE_MODEL_BAR = 3e-2          # golden_util.compare_grads
 
@@ -130,6 +132,80 @@ def test_output_heads_self_consistent():
     raw = synth.normal((4, 8, 6, 5), 6)
     st64, st32 = S.ref_bn_stats(raw), S.ref_bn_stats(raw, torch.float32)
     S.compare("stats", st32, st64, st32)
+
+
+def loss_link_case(b=3, n_rot=4):
+    """Nine outputs and the targets of a step at small sizes (map 16 x 16, score levels 2 x 2 .. 7 x 7)."""
+    hw = 16
+    outs = [synth.normal((b, hw * hw), 1, std=3.0), None, F.normalize(synth.normal((b, 2, hw, hw), 2), dim=1)]
+    outs[1] = torch.softmax(outs[0], dim=1).reshape(b, 1, hw, hw)
+    labels = []
+    for j in range(6):
+        side = 2 + j
+        outs.append(synth.uniform((b, n_rot, side, side), 10 + j, -1.0, 1.0))
+        labels.append(synth.uniform((b, n_rot, side, side), 20 + j) ** 3)
+    labels[2][0] *= 0.03                       # level 3: one sample with little label mass
+    gt = synth.uniform((b, 1, hw, hw), 30) ** 8
+    gt_flat = gt.flatten(1) / gt.flatten(1).sum(1, keepdim=True)
+    gt_ori = F.normalize(synth.normal((b, 2, hw, hw), 31), dim=1)
+    return outs, (gt, gt_flat, gt_ori, labels)
+
+
+class _Rec(object):
+    tape = None
+
+
+def test_loss_link_self_consistent_and_mutations():
+    """The loss link on a recorded step made of the float32 reference itself: it passes; a heat-map gradient is refused; one
+    score level's gradient scaled as if the batch's label mass D had lost one row of three, and the value of the mix with
+    infoNCE summed over five levels, are each caught by name."""
+    outs, targets = loss_link_case()
+    r64, r32 = S.ref_loss_mix(outs, targets), S.ref_loss_mix(outs, targets, dtype=torch.float32)
+    assert set(r64) == {"out:loss"} | set("din:" + n for n in S.LOSS_OUTPUTS.values()) and r64["out:loss"].dtype == torch.float64
+    want = (O.cross_entropy_loss(outs[0].double(), targets[1].double()) + 1e1 * O.orientation_loss(outs[2].double(), targets[2].double(), targets[0].double())
+            + 1e4 * sum(O.infonce_loss(outs[3 + j].double().flatten(1), targets[3][j].double().flatten(1)) for j in range(6)) / 6)
+    assert abs(float(r64["out:loss"] - want)) <= 1e-12 * abs(float(want))
+    rec = _Rec()
+    rec.outs = outs
+    rec.gout = [r32["din:logits"], None, r32["din:ori"]] + [r32["din:scores%d" % (j + 1)] for j in range(6)]
+
+    def link(gout, loss, want_key=None):
+        rec.gout = gout
+        chk = S.StepChecker(rec, {}, {}, want_key)
+        chk.loss_link(targets, loss)
+        return chk
+    good = list(rec.gout)
+    chk = link(good, float(r32["out:loss"]))
+    chk.report.assert_ok()
+    assert chk.stages == ["loss"] and chk.report.tensors() == 9 and not chk.loss_left_out and not chk.loss_crosschecks
+    chk = link(good[:1] + [torch.zeros_like(outs[1])] + good[2:], float(r32["out:loss"]))
+    chk.report.assert_ok()
+    with pytest.raises(AssertionError, match="heat-map"):
+        link(good[:1] + [1e-9 * torch.ones_like(outs[1])] + good[2:], float(r32["out:loss"]))
+    with pytest.raises(AssertionError, match="received no gradient"):
+        link(good[:5] + [None] + good[6:], float(r32["out:loss"]))
+    # an output left out of the gradient comparison still enters the value
+    chk = link(good, float(r32["out:loss"]), lambda key: key != ("loss", 8))
+    chk.report.assert_ok()
+    assert chk.loss_left_out == ["scores6"] and chk.report.tensors() == 8
+    assert link(good, float(r32["out:loss"]), lambda key: key[0] != "loss").stages == []
+    # mutations
+    lab = targets[3][2]
+    den = torch.where(lab > 1e-2, lab, torch.zeros_like(lab)).flatten(1).sum(1).double()
+    light = int(den.argmin())
+    scale = float(den.sum() / (den.sum() - den[light]))
+    bad = list(good)
+    bad[5] = good[5] * scale
+    print("loss link: a row's label mass missing from D scales the level's gradient by %.5f" % scale)
+    assert light == 0 and 1e-3 < scale - 1 < WHOLE_MODEL_BAR
+    chk = link(bad, float(r32["out:loss"]))
+    failed = [r[1] for r in chk.report.failures()]
+    assert failed and all(name.startswith("din:scores3") for name in failed), failed
+    nce5 = sum(O.infonce_loss(outs[3 + j].flatten(1), targets[3][j].flatten(1)) for j in range(5))
+    five = float(r32["out:loss"]) - 1e4 * float(O.infonce_loss(outs[8].flatten(1), targets[3][5].flatten(1))) / 6
+    assert abs(five - float(O.cross_entropy_loss(outs[0], targets[1]) + 1e4 * nce5 / 6 + 1e1 * O.orientation_loss(outs[2], targets[2], targets[0]))) < 1e-2
+    failed = [r[1] for r in link(good, five).report.failures()]
+    assert failed and all(name.startswith("out:loss") for name in failed), failed
 
 
 def test_adapters_round_trip():

@@ -8,6 +8,13 @@ gradient the stage owns (the step's final .grad) equal the fp64 VJP of the recor
 max(floor, 4 * e_ref), floor 1e-4 (forward, statistics) / 2e-4 (gradients), e_ref = the reference's own fp32 error on the same
 inputs.  The full-coverage cases also assert that the parameters checked are exactly the parameters with a gradient.
 
+The chain starts at the loss (StepChecker.loss_link, stage `loss`): the loss value and the gradients the loss kernels put on the
+outputs against the benched mix restated on the recorded outputs, so the teacher-forced links below it no longer take `gout` as
+given.  The B = 64 case compares every output of at most B64_MAX_ELEMENTS elements, all but level 6's scores (printed; its row
+length is covered by tests/test_losses_gpu.py).  Outputs above 4 Mi elements are restated in float64 on the device and a
+two-sample sub-batch recomputed on the CPU must agree to 1e-12.  The link adds 0.3 s / 0.04 s / 1.1 s to the B = 4 / B = 3 /
+B = 64 case (profiles/r13/loss_checks.txt, with the wall times of every test of this file before and after).
+
 The printed table (worst e_got / e_ref / bar per stage kind and case, and the B = 64 stage set) is kept in
 profiles/r08/stage_checks.txt, with the wall times.  Wall-time rule: a test of this file should not be slower than the slowest
 test the suite had before (27 s); the two trims provided for that were both taken (ori_prior: matching levels only; the B = 64
@@ -36,7 +43,8 @@ def _step(net, grd, sat, masks, center, angle, n_rot):
     from ccvpe_amd import losses, targets
     for p in net.parameters():
         p.grad = None
-    gt, gt_flat, gt_ori, labels = targets.train_targets(center, angle, n_rot)
+    built = targets.train_targets(center, angle, n_rot)
+    gt, gt_flat, gt_ori, labels = built
     out = net(grd, sat, drop_masks=masks)
     nce = 0.0
     for lvl in range(6):
@@ -44,7 +52,7 @@ def _step(net, grd, sat, masks, center, angle, n_rot):
     loss = losses.cross_entropy_loss(out[0], gt_flat) + 1e4 * nce / 6 + 1e1 * losses.orientation_loss(out[2], gt_ori, gt)
     loss.backward()
     torch.cuda.synchronize()
-    return float(loss.detach()), {n: p.grad.detach().clone() for n, p in net.named_parameters() if p.grad is not None}
+    return float(loss.detach()), {n: p.grad.detach().clone() for n, p in net.named_parameters() if p.grad is not None}, built
 
 
 def _drop_masks(batch, seed):
@@ -77,7 +85,7 @@ def _run_case(synth_sd, monkeypatch, label, kind, batch, ori_noise=None, want=No
     t0 = time.time()
     with monkeypatch.context() as mp:
         rec = S.Recorder(mp, keep=keep or want)
-        loss, grads = _step(net, grd, sat, masks, center, angle, n_rot)
+        loss, grads, built = _step(net, grd, sat, masks, center, angle, n_rot)
     assert loss == loss and rec.tape is not None and rec.gout is not None
     for (enc, i), m in masks.items():
         if S.skip_block(i) and i:
@@ -85,10 +93,14 @@ def _run_case(synth_sd, monkeypatch, label, kind, batch, ori_noise=None, want=No
     t1 = time.time()
     named = {n: p.detach() for n, p in net.named_parameters()}
     chk = S.StepChecker(rec, named, grads, want)
-    report = chk.run_all(bool(rec.tape["circular"]))
+    report = chk.run_all(bool(rec.tape["circular"]), built, loss)
     report.finish()
     lines = ["== %s: loss %.6f, %d stages, %d tensors compared (%d noise-level), step %.1f s, references %.1f s"
              % (label, loss, len(set(chk.stages)), report.tensors(), len(report.noise), t1 - t0, time.time() - t1)]
+    if "loss" in chk.stages:
+        lines.append("  loss link: %.2f s of the references; outputs left out: %s; float64 on the device (cross-checked on two samples "
+                     "against the CPU: value, gradient): %s" % (chk.loss_seconds, ", ".join(chk.loss_left_out) or "none",
+                                                                ", ".join("%s %.1e %.1e" % c for c in chk.loss_crosschecks) or "none"))
     for kindname, (e_got, e_ref, bar, stage, tensor) in sorted(report.worst_by_kind().items()):
         lines.append("  %-16s worst e_got %.3e  e_ref %.3e  bar %.3e   (%s %s)" % (kindname, e_got, e_ref, bar, stage, tensor))
     if report.noise:
@@ -115,7 +127,8 @@ def _full_coverage(chk, report, grads):
     kinds = [S.stage_kind(s) for s in set(chk.stages)]
     assert (kinds.count("stem"), kinds.count("block"), kinds.count("head"), kinds.count("match"),
             kinds.count("dec_loc") + kinds.count("dec_ori")) == (2, 32, 2, 6, 12), sorted(set(chk.stages))
-    assert {"gdesc", "sdesc", "head_softmax", "head_normalize"} <= set(chk.stages)
+    assert {"gdesc", "sdesc", "head_softmax", "head_normalize", "loss"} <= set(chk.stages)
+    assert not chk.loss_left_out, chk.loss_left_out
     assert len([s for s in set(chk.stages) if s.startswith("skipsum")]) == 5 and {"dgdesc", "catsum:1"} <= set(chk.stages)
 
 
@@ -175,9 +188,15 @@ def b64_stage_set(kind, batch, limit):
         sizes[("match", j)] = batch * spec["loc"][j][0] * hw * hw
         hw *= 2
     sizes[("heads",)] = batch * 512 * 512 * 2
+    # the loss link: one key per output the mix reads (logits, orientation field, scores of level 1 .. 6), its own elements
+    sizes[("loss", 0)], sizes[("loss", 2)] = batch * 512 * 512, batch * 2 * 512 * 512
+    for j in range(6):
+        sizes[("loss", 3 + j)] = batch * spec["n_rot"] * (8 << j) ** 2
     for key, n in sizes.items():
         if n <= limit:
             keep.add(key)
+    if any(k[0] == "loss" for k in keep):
+        keep.add(("loss",))
     return keep, sizes
 
 
@@ -191,6 +210,9 @@ def _describe(keys):
     for branch in ("loc", "ori"):
         out.append("%s decoder levels %s" % (branch, sorted(k[2] + 1 for k in keys if k[0] == "dec" and k[1] == branch)))
     out.append("output heads %s" % (("heads",) in keys))
+    out.append("loss link on %s (left out: %s)" % (
+        [S.LOSS_OUTPUTS[i] for i in sorted(S.LOSS_OUTPUTS) if ("loss", i) in keys],
+        [S.LOSS_OUTPUTS[i] for i in sorted(S.LOSS_OUTPUTS) if ("loss", i) not in keys] or "nothing"))
     return "; ".join(out)
 
 
@@ -203,7 +225,11 @@ def test_b64_stage_set_from_shapes():
     for branch in ("loc", "ori"):
         assert sorted(k[2] for k in keys if k[0] == "dec" and k[1] == branch) == [0, 1, 2]
     assert {("match", 0), ("match", 1), ("match", 2)} <= keys and ("match", 5) not in keys
+    assert sizes[("loss", 8)] == 64 * 20 * 256 * 256 and ("loss", 8) not in keys and ("loss",) in keys
     keys, sizes = b64_stage_set("vigor", 64, B64_MAX_ELEMENTS)
+    # the loss link: every output but level 6's scores (84 Mi elements; its row length is covered by tests/test_losses_gpu.py)
+    assert sorted(k[1] for k in keys if k[0] == "loss" and len(k) == 2) == [0, 2, 3, 4, 5, 6, 7] and ("loss",) in keys
+    assert sizes[("loss", 2)] == B64_MAX_ELEMENTS
     print("B = 64 stage set (largest activation <= %d elements): %s" % (B64_MAX_ELEMENTS, _describe(keys)))
     assert set(range(12, 16)) <= set(k[2] for k in keys if k[0] == "block" and k[1] == "sat_efficientnet")
     assert {6, 7, 8, 12, 13, 14, 15} <= set(k[2] for k in keys if k[0] == "block" and k[1] == "grd_efficientnet")
@@ -226,7 +252,9 @@ def test_stages_of_the_benched_step_b64(synth_sd, monkeypatch):
     chk, report, grads, rec = _run_case(synth_sd, monkeypatch, "CVM_VIGOR B=64", "vigor", 64, want=lambda key: key in keys,
                                         keep=keep, seed=3)
     report.assert_ok()
-    assert len(set(chk.stages)) >= len(keys)
+    print("B = 64 loss link: outputs left out: %s" % chk.loss_left_out)
+    assert "loss" in chk.stages and chk.loss_left_out == ["scores6"]
+    assert len(set(chk.stages)) >= len([k for k in keys if k[0] != "loss"]) + 1      # the loss keys are one stage
 
 
 def _print_premises(rec):
