@@ -17,7 +17,8 @@ uint8 images (3-6 MB per pair) plus three scalars per sample to the device, wher
 KITTI (datasets.py:354-640, train_KITTI.py:46-100): `KITTIPairs(root, file, ...)` reads the split file, the OXTS heading and
 the two images of a sample and performs the aerial image's geometric alignment — rotate to the vehicle heading, shift to the
 camera, the random (training) or listed (test files) shift and rotation, centre crop — with the same PIL calls as the reference
-(PIL's affine resampling is host work either way; the result is the 512 x 512 uint8 crop).  Resize + normalise of both images
+(the result is the 512 x 512 uint8 crop), or, with `device_align=True`, leaves the alignment to ONE ccvpe_kitti_align_u8 launch per
+batch that DeviceBatches makes on the decoded maps (ccvpe_amd/align.py, csrc/align.hip: bit-identical to the PIL calls).  Resize + normalise of both images
 and the 1 + 16 + 2 channel ground truth then run on the device exactly as for VIGOR:
 
     pairs = KITTIPairs(root, "train_files.txt", shift_range_lat=20, shift_range_lon=20, rotation_range=10)
@@ -171,10 +172,15 @@ class KITTIPairs(object):
     sample's fixed perturbation: `<name> <shift_x> <shift_y> <theta>` (test=True).  Training perturbations are three uniform
     draws in [-1, 1) per sample — from numpy's global generator when rng is None (so `np.random.seed(s)` reproduces the
     reference's sequence sample by sample when samples are drawn in order: sample() called sequentially, or DeviceBatches, which
-    calls draw() in index order on one thread), else from `rng` (a numpy Generator / RandomState; draws are serialised by a lock)."""
+    calls draw() in index order on one thread), else from `rng` (a numpy Generator / RandomState; draws are serialised by a lock).
 
-    def __init__(self, root, file, shift_range_lat=20.0, shift_range_lon=20.0, rotation_range=10.0, test=False, rng=None):
-        self.root, self.test = root, bool(test)
+    device_align=True leaves the alignment to the device: sample() returns the map AS DECODED (`sat_src_u8`) and the parameter row
+    of ccvpe_amd/align.py (`align`) instead of `sat_u8`; DeviceBatches then aligns the whole batch with one launch of
+    ccvpe_kitti_align_u8, bit-identical to the Pillow calls.  Every other key, and every draw, is the same."""
+
+    def __init__(self, root, file, shift_range_lat=20.0, shift_range_lon=20.0, rotation_range=10.0, test=False, rng=None,
+                 device_align=False):
+        self.root, self.test, self.device_align = root, bool(test), bool(device_align)
         self.meter_per_pixel = kitti_meter_per_pixel()
         self.shift_px_lat = shift_range_lat / self.meter_per_pixel
         self.shift_px_lon = shift_range_lon / self.meter_per_pixel
@@ -211,7 +217,8 @@ class KITTIPairs(object):
 
     def sample(self, idx, sat_hw=(512, 512), grd_hw=(256, 1024), draws=None):
         """Decode + align sample idx.  Returns the dict DeviceBatches consumes: grd_u8 (the left camera image as decoded),
-        sat_u8 (the aligned, perturbed 512 x 512 aerial crop), roll = 0, angle_deg (orientation ground truth in [0, 360]),
+        sat_u8 (the aligned, perturbed 512 x 512 aerial crop; device_align: sat_src_u8 and align in its place), roll = 0, angle_deg
+        (orientation ground truth in [0, 360]),
         center = (x_offset, y_offset) of the Gaussian (datasets.py:475-476), city = the drive, index."""
         from PIL import Image
         name = self.lines[idx].split(" ")[0] if self.test else self.lines[idx]
@@ -224,17 +231,22 @@ class KITTIPairs(object):
             grd = np.array(im.convert("RGB"))
         sx, sy, ori = self.perturbation(idx) if draws is None else draws
         mpp = self.meter_per_pixel
-        sat = sat.rotate(-heading / np.pi * 180)                                    # east = the vehicle heading
-        sat = sat.transform(sat.size, Image.AFFINE, (1, 0, KITTI_CAMERA_SHIFT[0] / mpp, 0, 1, KITTI_CAMERA_SHIFT[1] / mpp),
-                            resample=Image.BILINEAR)
-        sat = sat.transform(sat.size, Image.AFFINE, (1, 0, sx * self.shift_px_lon, 0, 1, -sy * self.shift_px_lat),
-                            resample=Image.BILINEAR)
-        sat = sat.rotate(ori)
         w, h = sat.size
         if w < KITTI_CROP or h < KITTI_CROP:
             raise ValueError("%s: aerial map %dx%d is smaller than the %d crop" % (sat_path, w, h, KITTI_CROP))
-        left, top = int(round((w - KITTI_CROP) / 2.0)), int(round((h - KITTI_CROP) / 2.0))     # torchvision center_crop
-        sat = np.array(sat.crop((left, top, left + KITTI_CROP, top + KITTI_CROP)))
+        cam_px = (KITTI_CAMERA_SHIFT[0] / mpp, KITTI_CAMERA_SHIFT[1] / mpp)
+        shift_px = (sx * self.shift_px_lon, -sy * self.shift_px_lat)
+        if self.device_align:
+            from . import align
+            aerial = dict(sat_src_u8=np.array(sat),
+                          align=align.kitti_align_params(heading, cam_px, shift_px, ori, w, h, KITTI_CROP))
+        else:
+            sat = sat.rotate(-heading / np.pi * 180)                                # east = the vehicle heading
+            sat = sat.transform(sat.size, Image.AFFINE, (1, 0, cam_px[0], 0, 1, cam_px[1]), resample=Image.BILINEAR)
+            sat = sat.transform(sat.size, Image.AFFINE, (1, 0, shift_px[0], 0, 1, shift_px[1]), resample=Image.BILINEAR)
+            sat = sat.rotate(ori)
+            left, top = int(round((w - KITTI_CROP) / 2.0)), int(round((h - KITTI_CROP) / 2.0))     # torchvision center_crop
+            aerial = dict(sat_u8=np.array(sat.crop((left, top, left + KITTI_CROP, top + KITTI_CROP))))
         c, s_ = np.cos(ori / 180 * np.pi), np.sin(ori / 180 * np.pi)
         x_off = int(sx * self.shift_px_lon * c - sy * self.shift_px_lat * s_)       # int(): truncation, as the reference
         y_off = int(-sy * self.shift_px_lat * c - sx * self.shift_px_lon * s_)
@@ -243,7 +255,7 @@ class KITTIPairs(object):
             angle += 360
         elif angle > 360:
             angle -= 360
-        return dict(grd_u8=grd, sat_u8=sat, roll=0, angle_deg=float(angle), center=(float(x_off), float(y_off)),
+        return dict(grd_u8=grd, **aerial, roll=0, angle_deg=float(angle), center=(float(x_off), float(y_off)),
                     city=name[:38], index=int(idx))
 
 
@@ -404,6 +416,7 @@ class DeviceBatches(object):
         self.grd_hw, self.sat_hw, self.fov = tuple(grd_hw), tuple(sat_hw), fov
         self.keep_w = int(grd_hw[1] * fov / 360)                              # train_VIGOR.py:177: int(w * FoV / 360)
         self.targets, self.n_bins, self.drop_last, self.ascending_bins = targets, n_bins, drop_last, bool(ascending_bins)
+        self._stage, self._stage_free = None, None          # device alignment: the pinned staging buffer and its upload's event
 
     def __len__(self):
         n = len(self.indices)
@@ -414,6 +427,26 @@ class DeviceBatches(object):
         draws = [self.pairs.draw(int(i)) for i in chunk]
         return list(pool.map(lambda a: self.pairs.sample(int(a[0]), self.sat_hw, self.grd_hw, draws=a[1]), zip(chunk, draws)))
 
+    def _align_on_device(self, samples):
+        """KITTIPairs(device_align=True): the batch's decoded maps packed into ONE pinned staging buffer (reused across batches),
+        one upload, the parameter rows, one ccvpe_kitti_align_u8 launch -> [B, 512, 512, 3] uint8 crops on the device."""
+        from . import align
+        sizes = [s["sat_src_u8"].size for s in samples]
+        offsets = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        total = int(offsets[-1])
+        if self._stage is None or self._stage.numel() < total:
+            self._stage = torch.empty((total,), dtype=torch.uint8).pin_memory()
+        elif self._stage_free is not None:
+            self._stage_free.synchronize()                   # the previous batch's upload has read the buffer
+        stage = self._stage.numpy()
+        for s, o, n in zip(samples, offsets, sizes):
+            stage[o:o + n] = s["sat_src_u8"].reshape(-1)
+        src = self._stage[:total].to(self.device, non_blocking=True)
+        self._stage_free = torch.cuda.Event()
+        self._stage_free.record()
+        rows = torch.from_numpy(np.stack([s["align"] for s in samples])).to(self.device)
+        return align.kitti_align(src, torch.from_numpy(offsets[:-1].copy()).to(self.device), rows, (KITTI_CROP, KITTI_CROP))
+
     def _to_device(self, samples):
         from . import preprocess, targets
         dev = self.device
@@ -421,9 +454,10 @@ class DeviceBatches(object):
         out = Batch()
         out.grd = torch.empty((b, 3, self.grd_hw[0], self.keep_w), device=dev, dtype=torch.float32)
         out.sat = torch.empty((b, 3) + self.sat_hw, device=dev, dtype=torch.float32)
+        crops = self._align_on_device(samples) if b and "align" in samples[0] else None
         for i, s in enumerate(samples):
             g = torch.from_numpy(s["grd_u8"]).to(dev, non_blocking=True)
-            a = torch.from_numpy(s["sat_u8"]).to(dev, non_blocking=True)
+            a = torch.from_numpy(s["sat_u8"]).to(dev, non_blocking=True) if crops is None else crops[i]
             preprocess.preprocess(g, self.grd_hw, dst=out.grd[i], roll=s["roll"], keep_w=self.keep_w)
             preprocess.preprocess(a, self.sat_hw, dst=out.sat[i])
         out.angle_deg = torch.tensor([s["angle_deg"] for s in samples], device=dev, dtype=torch.float32)

@@ -645,6 +645,18 @@ int ccvpe_preprocess_u8_f32(const unsigned char* src, int in_h, int in_w, const 
                             void* stream);
 
 /* -------------------------------------------------------------------------------------------
+ * KITTI aerial alignment (csrc/align.hip; the reference's datasets.py:443-464 / :577-596): PIL's rotate (NEAREST, 16.16
+ * fixed point) -> two BILINEAR translations (float64, truncated) -> rotate -> centre crop, evaluated lazily per pixel
+ * of the crop, bit-identical to Pillow.  ONE launch per batch.
+ *   src: packed uint8 buffer (device) of src_bytes bytes holding the decoded [h][w][3] maps; offsets [batch] int64 =
+ *   each sample's first byte; rows [batch][20] int64 = ccvpe_amd/align.py kitti_align_params (12 fixed-point integers,
+ *   4 float64 bit patterns, w, h, left, top), sizes may differ per sample; dst [batch][crop_h][crop_w][3] uint8.
+ *   A sample that does not fit in the buffer behind its offset is written as zeros and never read.
+ * ----------------------------------------------------------------------------------------- */
+int ccvpe_kitti_align_u8(const unsigned char* src, long src_bytes, const long long* offsets, const long long* rows,
+                         int batch, unsigned char* dst, int crop_h, int crop_w, void* stream);
+
+/* -------------------------------------------------------------------------------------------
  * bf16 storage variants (BASELINE configs C2 / C4).  Same kernels instantiated for bf16 NHWC
  * activations and bf16 packed weights (kpad a multiple of 32), fp32 accumulation on
  * v_mfma_f32_16x16x32_bf16, fp32 scale/shift/gate/bias, round-to-nearest-even on store.  Pointers
