@@ -5,6 +5,7 @@
 #include <cstdio>
 
 #include "../../include/ccvpe_hip.h"
+#include "dev_cache.h"
 
 namespace ccvpe {
 
@@ -21,6 +22,26 @@ inline int fail(int code, const char* fmt, ...) {
 inline int check_launch(const char* what) {
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(CCVPE_ELAUNCH, "%s: %s", what, hipGetErrorString(e));
+  return CCVPE_OK;
+}
+
+// Launch state is per DEVICE: the device that is current at call time is the one launched on, and each launcher keeps one
+// static DevCache per kernel instantiation (as it kept one flag before), so a second GPU in the process gets its own opt-in.
+
+// compute units of the current device; 256 (an MI355X) when the query fails.  host_state.hip
+int num_cus();
+
+// Opt kernel `kern` in to `bytes` of dynamic LDS on the current device, once per device and size: requests up to 48 KB need
+// no opt-in, and the driver call is skipped when `cache` already covers `bytes` there.
+template <typename K>
+inline int ensure_dyn_lds(DevCache& cache, K kern, int bytes, const char* what) {
+  if (bytes <= 48 * 1024) return CCVPE_OK;
+  int dev = -1;
+  if (hipGetDevice(&dev) != hipSuccess) dev = -1;          // not cached: the attribute call below reports what is wrong
+  if (cache.covers(dev, bytes)) return CCVPE_OK;
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  if (e != hipSuccess) return fail(CCVPE_ELAUNCH, "%s: set smem attr: %s", what, hipGetErrorString(e));
+  cache.raise(dev, bytes);
   return CCVPE_OK;
 }
 

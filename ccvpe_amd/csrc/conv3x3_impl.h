@@ -552,13 +552,9 @@ static int launch3x3_nw(const IgemmParams& p0, int batch, int variant, hipStream
     }
   }
 #endif
-  static bool attr_set[2] = {false, false};             // per (T, tile) instantiation of this launcher: one flag per kernel variant
+  static DevCache lds_set[2];                           // per (T, tile) instantiation of this launcher: one per kernel variant
   auto go = [&](int slot, void (*kern)(const IgemmParams), int lds) -> int {
-    if (!attr_set[slot] && lds > 48 * 1024) {
-      hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-      if (e != hipSuccess) return fail(CCVPE_ELAUNCH, "conv3x3: set smem attr: %s", hipGetErrorString(e));
-      attr_set[slot] = true;
-    }
+    if (int rc = ensure_dyn_lds(lds_set[slot], kern, lds, "conv3x3")) return rc;
     hipLaunchKernelGGL(kern, dim3(p.tiles_total), dim3(64 * NW), lds, stream, p);
     return CCVPE_OK;
   };

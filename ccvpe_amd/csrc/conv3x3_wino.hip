@@ -276,12 +276,8 @@ extern "C" int ccvpe_conv3x3_wino_f32(const ccvpe_conv_desc* d, void* stream) {
   const long total = (long)p.tiles_x * p.tiles_y * d->batch * p.tiles_n;
   if (total > 0x7fffffffL) return fail(CCVPE_EINVAL, "conv3x3_wino: grid too large");
   p.tiles_total = (int)total;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)conv3x3_wino_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, WG_LDS);
-    if (e != hipSuccess) return fail(CCVPE_ELAUNCH, "conv3x3_wino: set smem attr: %s", hipGetErrorString(e));
-    attr_set = true;
-  }
+  static DevCache lds_set;
+  if (int rc = ensure_dyn_lds(lds_set, conv3x3_wino_kernel, WG_LDS, "conv3x3_wino")) return rc;
   hipLaunchKernelGGL(conv3x3_wino_kernel, dim3(p.tiles_total), dim3(64 * WG_NW), WG_LDS, (hipStream_t)stream, p);
   return check_launch("conv3x3_wino_kernel");
 }

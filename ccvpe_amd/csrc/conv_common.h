@@ -278,7 +278,6 @@ template <typename T> int conv3x3_variant_query(const IgemmParams& p, int batch,
 extern bool g_use_pw2;                                    // ccvpe_set_pw_ring_kernels (conv_igemm.hip)
 template <typename T> bool pw2_supported(const IgemmParams& p, int mt, int nt, int wn);
 template <typename T> int pw2_dispatch(const IgemmParams& p, int mt, int nt, int wn, hipStream_t stream);
-int num_cus();                                            // narrow_bf16.hip
 // narrow_bf16.hip: bf16 3x3 layers with few channels on large images — weights resident in registers, persistent workgroups
 extern bool g_use_narrow;                                 // ccvpe_set_narrow_kernels (conv_igemm.hip)
 int c3n_supported(const IgemmParams& p, int batch);      // 0 = not served, else an instantiation id

@@ -390,12 +390,8 @@ static int launch_pw2(const IgemmParams& p0, hipStream_t stream) {
   p.tiles_total = (p.M / G::BM) * p.tiles_n;
   const int lds = G::lds_bytes(GATED, p.c0);
   if (lds > PW2_LDS) return fail(CCVPE_EINVAL, "pw2: tile <%d,%d,%d> does not fit the LDS", MT, NT, WN);
-  static int attr_lds = 0;                                // per instantiation: the largest size asked for so far
-  if (lds > attr_lds) {
-    hipError_t e = hipFuncSetAttribute((const void*)pw2_kernel<T, MT, NT, WN, ACT, GATED, RES, PW2_NSTG>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return fail(CCVPE_ELAUNCH, "pw2: set smem attr: %s", hipGetErrorString(e));
-    attr_lds = lds;
-  }
+  static DevCache lds_set;                                // per instantiation: the largest size asked for so far
+  if (int rc = ensure_dyn_lds(lds_set, pw2_kernel<T, MT, NT, WN, ACT, GATED, RES, PW2_NSTG>, lds, "pw2")) return rc;
   const int cus = num_cus();
   const int grid = p.tiles_total < 2 * cus ? (p.tiles_total + 7) / 8 * 8 : 2 * cus / 8 * 8;
   hipLaunchKernelGGL((pw2_kernel<T, MT, NT, WN, ACT, GATED, RES, PW2_NSTG>), dim3(grid), dim3(256), lds, stream, p);

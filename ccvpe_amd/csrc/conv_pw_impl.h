@@ -351,13 +351,8 @@ static int launch_pw_act(const IgemmParams& p0, hipStream_t stream) {
   static const int stagger = getenv("CCVPE_PW_STAGGER") ? atoi(getenv("CCVPE_PW_STAGGER")) : 0;   // x 1024 cycles
   p.ablate = ablate | (stagger << 8);
 #endif
-  static bool attr_set = false;               // one flag per instantiation
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)pw_gemm_kernel<T, MT, NT, WN, ACT>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       G::LDS_BYTES);
-    if (e != hipSuccess) return fail(CCVPE_ELAUNCH, "pw_gemm: set smem attr: %s", hipGetErrorString(e));
-    attr_set = true;
-  }
+  static DevCache lds_set;                    // one per instantiation
+  if (int rc = ensure_dyn_lds(lds_set, pw_gemm_kernel<T, MT, NT, WN, ACT>, G::LDS_BYTES, "pw_gemm")) return rc;
   // persistent grid: 2 workgroups per CU (LDS / VGPR budget of the kernel), a multiple of 8 so that the virtual-block ->
   // XCD map is stable over a workgroup's iterations
   int grid = p.tiles_total < 512 ? (p.tiles_total + 7) / 8 * 8 : 512;

@@ -494,12 +494,8 @@ static int conv_wgrad_impl(const float* src0, int c0, int ld0, const float* src1
   const bool sq = tn == 64 || big;
   const size_t lds = sizeof(float) * 2 * WG_BP * ((size_t)wgrad_pitch(tn, sq) + wgrad_pitch(tcw, sq));
   if (big) {
-    static bool attr_set = false;
-    if (!attr_set) {
-      hipError_t e = hipFuncSetAttribute((const void*)conv_wgrad_kernel<128, 128>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) return fail(CCVPE_ELAUNCH, "conv_wgrad: set smem attr: %s", hipGetErrorString(e));
-      attr_set = true;
-    }
+    static DevCache lds_set;
+    if (int rc = ensure_dyn_lds(lds_set, conv_wgrad_kernel<128, 128>, (int)lds, "conv_wgrad")) return rc;
     hipLaunchKernelGGL((conv_wgrad_kernel<128, 128>), dim3((unsigned)blocks), dim3(256), lds, st, p);
   } else if (gate) {
     if (tn == 16) hipLaunchKernelGGL((conv_wgrad_kernel<16, 64, true>), dim3((unsigned)blocks), dim3(256), lds, st, p);

@@ -634,13 +634,9 @@ extern "C" int ccvpe_se_gate_f32(const float* part, int nblk, float inv_hw, cons
   int g = (256 + B - 1) / B;                 // workgroups per sample (see the kernel's comment)
   g = g < 1 ? 1 : (g > slices ? slices : g);
   const int cpw = (((C + g - 1) / g) + 3) & ~3;        // channels per workgroup
-  static bool attr_set = false;
-  if (!attr_set && smem > 48 * 1024) {
-    if (hipFuncSetAttribute((const void*)se_gate_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024) != hipSuccess)
-      return fail(CCVPE_ELAUNCH, "se_gate: set smem attr");
-    attr_set = true;
-  }
   if (smem > 64 * 1024) return fail(CCVPE_EINVAL, "se_gate: C = %d is too wide", C);
+  static DevCache lds_set;
+  if (int rc = smem > 48 * 1024 ? ensure_dyn_lds(lds_set, se_gate_kernel, 64 * 1024, "se_gate") : CCVPE_OK) return rc;
   hipLaunchKernelGGL(se_gate_kernel, dim3((C + cpw - 1) / cpw, B), dim3(SE_THREADS), smem, (hipStream_t)stream, part,
                      nblk, inv_hw, w1, b1, w2, b2, gate, C, Cs, cpw);
   return check_launch("se_gate_kernel");

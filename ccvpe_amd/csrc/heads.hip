@@ -380,11 +380,6 @@ __global__ void loss_finish_kernel(const float* __restrict__ part, float* __rest
 
 using namespace ccvpe;
 
-thread_local char ccvpe::g_err[512] = "";
-
-extern "C" const char* ccvpe_last_error(void) { return g_err; }
-extern "C" int ccvpe_abi_version(void) { return 7; }
-
 extern "C" int ccvpe_ground_descriptor_f32(const float* y1, int ld, const float* wh, const float* bh, const int* cd,
                                            float* out, int B, int h, int w, void* stream) {
   if (!cd || B <= 0 || h <= 0 || w <= 0) return fail(CCVPE_EINVAL, "ground_descriptor: bad args");

@@ -546,8 +546,6 @@ __global__ __launch_bounds__(256) void match_stream_kernel(const MatchStreamPara
   }
 }
 
-int num_cus();   // narrow_bf16.hip
-
 }  // namespace ccvpe
 
 using namespace ccvpe;
@@ -566,12 +564,8 @@ static int launch_match(const TX* x, int ldx, const float* g, int ldg, int L, co
   const size_t smem = sizeof(float) * ((size_t)tl * (PARTIAL ? 2 : 1) + (size_t)tp * S + (size_t)n_shifts * tp + 2 * tp + 4 + pbuf);
   if (smem > 160 * 1024) return fail(CCVPE_EINVAL, "match_level: C=%d needs %zu B of LDS", C, smem);
   auto kern = match_kernel<TX, NPAD, PARTIAL, VEC, MFMA>;
-  static size_t attr_smem = 64 * 1024;             // per instantiation: the largest size asked for so far
-  if (smem > attr_smem) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    if (e != hipSuccess) return fail(CCVPE_ELAUNCH, "match_level: set smem attr: %s", hipGetErrorString(e));
-    attr_smem = smem;
-  }
+  static DevCache lds_set;                         // per instantiation: the largest size asked for so far
+  if (int rc = ensure_dyn_lds(lds_set, kern, (int)smem, "match_level")) return rc;
   if (B > 65535) return fail(CCVPE_EINVAL, "match_level: batch > 65535");
   dim3 grid((hw + tp - 1) / tp, B);
   hipLaunchKernelGGL(kern, grid, dim3(256), smem, st, x, ldx, g, ldg, L, mo, n_shifts, n_max, n_tail, scores, dstx,

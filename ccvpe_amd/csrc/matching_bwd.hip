@@ -338,10 +338,8 @@ static int launch_match_bwd(const float* x, int ldx, const float* g, int ldg, in
                                        (size_t)4 * 16 * ((NPAD + 15) / 16) * MBK + (L + 1) + 4);
   if (smem > 160 * 1024) return fail(CCVPE_EINVAL, "match_level_bwd: C=%d needs %zu B of LDS", C, smem);
   auto kern = match_bwd_kernel<NPAD>;
-  if (smem > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    if (e != hipSuccess) return fail(CCVPE_ELAUNCH, "match_level_bwd: set smem attr: %s", hipGetErrorString(e));
-  }
+  static DevCache lds_set;                      // per instantiation: the largest size asked for so far
+  if (int rc = ensure_dyn_lds(lds_set, kern, (int)smem, "match_level_bwd")) return rc;
   hipLaunchKernelGGL(kern, dim3(nblk, B, nslice), dim3(tpb), smem, st, x, ldx, g, ldg, L, mo, n_shifts, n_max, n_tail, scores,
                      dscores, ddst, ldo, dx, lddx, part, nblk, hw, C, nslice);
   return check_launch("match_bwd_kernel");

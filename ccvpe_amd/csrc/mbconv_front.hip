@@ -332,12 +332,8 @@ static int mbconv_front_any(const void* x, const void* w_exp, int kpad, const fl
   int rc = CCVPE_OK;
   auto go = [&](auto kern, int lds_floats) {
     const int lds = lds_floats * 4;
-    static bool attr_set = false;                    // per instantiation (generic lambda)
-    if (lds > 48 * 1024 && !attr_set) {
-      hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-      if (e != hipSuccess) { rc = fail(CCVPE_ELAUNCH, "mbconv_front: set smem attr: %s", hipGetErrorString(e)); return; }
-      attr_set = true;
-    }
+    static DevCache lds_set;                         // per instantiation (generic lambda)
+    if ((rc = ensure_dyn_lds(lds_set, kern, lds, "mbconv_front"))) return;
     hipLaunchKernelGGL(kern, dim3(p.total_blocks), dim3(256), lds, st, p);
   };
   // instantiated: the big tile for Cin <= 16 (one K piece in either storage type), the small tile for 1-3 pieces

@@ -33,8 +33,6 @@
 
 namespace ccvpe {
 
-int num_cus();   // narrow_bf16.hip
-
 int g_mbplane_mode = 7;
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -765,12 +763,14 @@ static bool mbband_plan(const MbpGeom& g, int H, int W, int cin, int mid, int k,
 }
 
 // the band-owner kernel (bf16, fused form): same bands as the geometry above (the squeeze-partial rows must not depend on the
-// kernel), its own CH = 16 row pitch, chunk groups so that the launch is about one workgroup per CU
+// kernel), its own CH = 16 row pitch, chunk groups so that the launch is about one workgroup per CU.
+// *taken = false with CCVPE_OK: the band kernel does not take the shape and nothing was launched
 static int mbband_launch(const MbpGeom& g, const void* x, const void* w_exp, int kpad, const float* s0, const float* b0,
                          const float* w_dw, const float* s1, const float* b1, void* y, float* se_partial, int B, int H, int W,
-                         int cin, int mid, int k, int stride, int circular, void* stream) {
+                         int cin, int mid, int k, int stride, int circular, void* stream, bool* taken) {
   MbBandPlan pl;
-  if (!mbband_plan(g, H, W, cin, mid, k, stride, B, &pl) || pl.nkk != kpad / 32) return -1000;
+  *taken = false;
+  if (!mbband_plan(g, H, W, cin, mid, k, stride, B, &pl) || pl.nkk != kpad / 32) return CCVPE_OK;
   const int tp = stride == 1 ? k - 1 : k - 2;
   const int Ho = (H + tp - k) / stride + 1, Wo = (W + tp - k) / stride + 1;
   const int XG = Wo / (stride == 1 ? 4 : 2);
@@ -790,24 +790,18 @@ static int mbband_launch(const MbpGeom& g, const void* x, const void* w_exp, int
   p.xg_magic = (unsigned)((1048576 + XG - 1) / XG);
   hipStream_t st = (hipStream_t)stream;
   int rc = CCVPE_OK;
-  bool launched = false;
   auto go = [&](auto kern) {
-    static bool attr_set = false;
-    if (!attr_set) {
-      hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (e != hipSuccess) { rc = fail(CCVPE_ELAUNCH, "mbconv_band: set smem attr: %s", hipGetErrorString(e)); return; }
-      attr_set = true;
-    }
+    static DevCache lds_set;                         // one per instantiation (generic lambda)
+    if ((rc = ensure_dyn_lds(lds_set, kern, 160 * 1024, "mbconv_band"))) return;
     hipLaunchKernelGGL(kern, dim3(p.total_blocks), dim3(512), lds, st, p);
-    launched = true;
+    *taken = true;
   };
-#define MBB(K_, S_, NKK_, TPW_, RY_) if (k == K_ && stride == S_ && nkk == NKK_ && tpwc == TPW_ && ry == RY_ && !launched && !rc) go(mbconv_band_kernel<K_, S_, NKK_, TPW_, RY_>);
+#define MBB(K_, S_, NKK_, TPW_, RY_) if (k == K_ && stride == S_ && nkk == NKK_ && tpwc == TPW_ && ry == RY_ && !*taken && !rc) go(mbconv_band_kernel<K_, S_, NKK_, TPW_, RY_>);
   MBB(3, 1, 3, 10, 2) MBB(5, 1, 3, 10, 2) MBB(3, 1, 4, 10, 2) MBB(5, 1, 4, 10, 2) MBB(5, 2, 3, 10, 2) MBB(5, 2, 4, 10, 2)
   MBB(3, 1, 3, 10, 1) MBB(5, 1, 3, 10, 1) MBB(3, 1, 4, 10, 1) MBB(5, 1, 4, 10, 1) MBB(5, 2, 3, 10, 1) MBB(5, 2, 4, 10, 1)
   MBB(3, 1, 6, 4, 1) MBB(5, 1, 6, 4, 1) MBB(5, 2, 6, 4, 1)
 #undef MBB
-  if (rc) return rc;
-  if (!launched) return -1000;
+  if (rc || !*taken) return rc;
   return check_launch("mbconv_band_kernel");
 }
 
@@ -838,8 +832,9 @@ static int mbplane_any(int expand, const void* x, const void* w_exp, int kpad, c
   if (circular && W < k) return fail(CCVPE_EINVAL, "mbconv_plane: W too small for circular wrap");
   if constexpr (sizeof(TE) == 2) {
     if (expand && (g_mbplane_mode & 4)) {
-      const int rc2 = mbband_launch(g, x, w_exp, kpad, s0, b0, w_dw, s1, b1, y, se_partial, B, H, W, cin, mid, k, stride, circular, stream);
-      if (rc2 != -1000) return rc2;                  // -1000: the band kernel does not take the shape
+      bool taken = false;
+      const int rc2 = mbband_launch(g, x, w_exp, kpad, s0, b0, w_dw, s1, b1, y, se_partial, B, H, W, cin, mid, k, stride, circular, stream, &taken);
+      if (taken || rc2 != CCVPE_OK) return rc2;      // else the band kernel does not take the shape: the plane kernel below
     }
   }
   MbPlaneParams p;
@@ -861,12 +856,8 @@ static int mbplane_any(int expand, const void* x, const void* w_exp, int kpad, c
   int rc = CCVPE_OK;
   bool launched = false;
   auto go = [&](auto kern) {
-    static bool attr_set = false;                    // one per instantiation (generic lambda): a driver call, not per launch
-    if (g.lds_bytes > 48 * 1024 && !attr_set) {
-      hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, MBP_LDS_MAX);
-      if (e != hipSuccess) { rc = fail(CCVPE_ELAUNCH, "mbconv_plane: set smem attr: %s", hipGetErrorString(e)); return; }
-      attr_set = true;
-    }
+    static DevCache lds_set;                         // one per instantiation (generic lambda): a driver call, not per launch
+    if (g.lds_bytes > 48 * 1024 && (rc = ensure_dyn_lds(lds_set, kern, MBP_LDS_MAX, "mbconv_plane"))) return;
     hipLaunchKernelGGL(kern, dim3(p.total_blocks), dim3(256), g.lds_bytes, st, p);
     launched = true;
   };

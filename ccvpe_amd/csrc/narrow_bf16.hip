@@ -3,16 +3,6 @@
 
 namespace ccvpe {
 
-int num_cus() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) n = v;
-    else n = 256;
-  }
-  return n;
-}
-
 // Which (CPT, NT) instantiation serves a 3x3 layer, or 0: 40 -> <= 48 (level 2 of the localisation decoder), 32 -> 32 (level 2 of
 // the orientation decoder, KITTI's level 2), 64 -> 64 (level 3 of the orientation decoder), 80 -> 80 (level 3 of the localisation
 // decoder: 276 weight registers per wave with the output channels split over two groups of waves).

@@ -439,8 +439,6 @@ __global__ __launch_bounds__(256, 1) void c3n_kernel(const NarrowParams p) {
   epilogue(tprev, last);
 }
 
-int num_cus();   // narrow_bf16.hip
-
 template <int CPT, int NT, int MT, bool WITH_MATCH = true, bool ILV = true, int NS = 1>
 static int launch_c3n(NarrowParams p, int batch, bool f32out, bool match, hipStream_t stream) {
   using G = C3nGeom<CPT, NT, MT, NS>;
@@ -457,13 +455,8 @@ static int launch_c3n(NarrowParams p, int batch, bool f32out, bool match, hipStr
     if constexpr (WITH_MATCH) kern = f32out ? c3n_kernel<CPT, NT, MT, true, true, ILV, NS> : c3n_kernel<CPT, NT, MT, false, true, ILV, NS>;
     else return fail(CCVPE_EINVAL, "c3n: the matching epilogue is not built for this tile");
   }
-  static int attr_lds[4] = {0, 0, 0, 0};
-  const int slot = (match ? 2 : 0) + (f32out ? 1 : 0);
-  if (attr_lds[slot] < lds) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return fail(CCVPE_ELAUNCH, "c3n_kernel: set smem attr: %s", hipGetErrorString(e));
-    attr_lds[slot] = lds;
-  }
+  static DevCache lds_set[4];                   // one per kernel variant: the largest size asked for so far
+  if (int rc = ensure_dyn_lds(lds_set[(match ? 2 : 0) + (f32out ? 1 : 0)], kern, lds, "c3n_kernel")) return rc;
   const int grid = (int)(total < num_cus() ? total : num_cus());
   hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, stream, p);
   return check_launch("c3n_kernel");
@@ -766,12 +759,8 @@ static int launch_up2(Up2Params p, int batch, hipStream_t stream) {
   if (total > 0x7fffffffL || total * (tiles_x > tiles_y ? tiles_x : tiles_y) >= (1L << 32)) return fail(CCVPE_EINVAL, "up2: grid too large");
   p.ti = make_tile_index(tiles_x, tiles_y, (int)total);
   p.ablate = narrow_ablate_env();
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)up2_kernel<CPT0, CPT1, NT, MT>, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES);
-    if (e != hipSuccess) return fail(CCVPE_ELAUNCH, "up2_kernel: set smem attr: %s", hipGetErrorString(e));
-    attr_set = true;
-  }
+  static DevCache lds_set;
+  if (int rc = ensure_dyn_lds(lds_set, up2_kernel<CPT0, CPT1, NT, MT>, G::LDS_BYTES, "up2_kernel")) return rc;
   const int grid = (int)(total < num_cus() ? total : num_cus());
   hipLaunchKernelGGL((up2_kernel<CPT0, CPT1, NT, MT>), dim3(grid), dim3(256), G::LDS_BYTES, stream, p);
   return check_launch("up2_kernel");

@@ -493,13 +493,8 @@ static int launch_tail(const TailParams& p0, int batch, hipStream_t stream) {
   const int max_wgs = 256 * 2 * 8;
   p.tiles_per_wg = PERSIST ? (int)((total + max_wgs - 1) / max_wgs) : 1;
   const int wgs = (int)((total + p.tiles_per_wg - 1) / p.tiles_per_wg);
-  static bool attr_set = false;                      // one flag per instantiation
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)tail512_kernel<T, COUT, NCH, TY, TX, WPP, SPLIT, PERSIST>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES);
-    if (e != hipSuccess) return fail(CCVPE_ELAUNCH, "tail512: set smem attr: %s", hipGetErrorString(e));
-    attr_set = true;
-  }
+  static DevCache lds_set;                           // one per instantiation
+  if (int rc = ensure_dyn_lds(lds_set, tail512_kernel<T, COUT, NCH, TY, TX, WPP, SPLIT, PERSIST>, G::LDS_BYTES, "tail512")) return rc;
   hipLaunchKernelGGL((tail512_kernel<T, COUT, NCH, TY, TX, WPP, SPLIT, PERSIST>), dim3(wgs), dim3(G::NTHR), G::LDS_BYTES, stream, p);
   return check_launch("tail512_kernel");
 }

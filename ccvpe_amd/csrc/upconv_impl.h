@@ -919,12 +919,8 @@ static int launch_up(const UpParams& p0, hipStream_t stream, int* route = nullpt
       constexpr bool PAIR = decltype(pair_tag)::value;
       using G = UpDmaGeom<T, MT, NT, WN, PAIR>;
       static_assert(G::LDS_BYTES <= 80 * 1024, "upconv_dma_kernel: two workgroups per CU");
-      static bool attr_set = false;                 // per (T, tile, PAIR) instantiation
-      if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)upconv_dma_kernel<T, MT, NT, WN, PAIR>, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES);
-        if (e != hipSuccess) return fail(CCVPE_ELAUNCH, "upconv_dma_kernel: set smem attr: %s", hipGetErrorString(e));
-        attr_set = true;
-      }
+      static DevCache lds_set;                      // per (T, tile, PAIR) instantiation
+      if (int rc = ensure_dyn_lds(lds_set, upconv_dma_kernel<T, MT, NT, WN, PAIR>, G::LDS_BYTES, "upconv_dma_kernel")) return rc;
       hipLaunchKernelGGL((upconv_dma_kernel<T, MT, NT, WN, PAIR>), dim3(p.tiles_total), dim3(256), G::LDS_BYTES, stream, p);
       return check_launch("upconv_dma_kernel");
     };

@@ -355,12 +355,8 @@ static int launch_s3(UpS3Params p, hipStream_t stream) {
   const long total = tiles_m * p.tiles_n * 4;
   if (total > 0x7fffffffL) return fail(CCVPE_EINVAL, "upconv_s3: grid too large");
   p.tiles_total = (int)total;
-  static bool attr_set = false;                 // per (tile, PAIR) instantiation
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)upconv_s3_kernel<MT, NT, WN, PAIR>, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES);
-    if (e != hipSuccess) return fail(CCVPE_ELAUNCH, "upconv_s3_kernel: set smem attr: %s", hipGetErrorString(e));
-    attr_set = true;
-  }
+  static DevCache lds_set;                      // per (tile, PAIR) instantiation
+  if (int rc = ensure_dyn_lds(lds_set, upconv_s3_kernel<MT, NT, WN, PAIR>, G::LDS_BYTES, "upconv_s3_kernel")) return rc;
   hipLaunchKernelGGL((upconv_s3_kernel<MT, NT, WN, PAIR>), dim3(p.tiles_total), dim3(256), G::LDS_BYTES, stream, p);
   return check_launch("upconv_s3_kernel");
 }

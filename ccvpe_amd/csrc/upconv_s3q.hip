@@ -337,12 +337,8 @@ static int launch_s3q(UpS3qParams p, hipStream_t stream) {
   using G = UpS3qGeom<NT>;
   static_assert(G::LDS_BYTES <= 80 * 1024, "upconv_s3q_kernel: two workgroups per CU");
   p.tiles_total = ((p.W1 + 15) / 16) * ((p.H1 + G::TH - 1) / G::TH) * p.batch;      // < 2^31: s3_refusal bounds the pixel count
-  static bool attr_set = false;                 // per instantiation
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)upconv_s3q_kernel<NT>, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES);
-    if (e != hipSuccess) return fail(CCVPE_ELAUNCH, "upconv_s3q_kernel: set smem attr: %s", hipGetErrorString(e));
-    attr_set = true;
-  }
+  static DevCache lds_set;                      // per instantiation
+  if (int rc = ensure_dyn_lds(lds_set, upconv_s3q_kernel<NT>, G::LDS_BYTES, "upconv_s3q_kernel")) return rc;
   hipLaunchKernelGGL((upconv_s3q_kernel<NT>), dim3(p.tiles_total), dim3(256), G::LDS_BYTES, stream, p);
   return check_launch("upconv_s3q_kernel");
 }

@@ -19,6 +19,12 @@
  *     safe: no allocation, no synchronisation, no host-side state).
  *   - return 0 on success, a negative CCVPE_E* code otherwise; ccvpe_last_error() gives the text.
  *     No C++ exception crosses the ABI.
+ *   - devices and threads: a process may drive any number of devices.  A call launches on the HIP
+ *     device that is current in the calling thread at call time (`stream` must belong to it).  What
+ *     the library remembers about a device (a kernel's dynamic-LDS opt-in, the CU count) is kept per
+ *     device ordinal in relaxed atomics: host threads may race on it, the worst case is a repeated
+ *     driver call.  The error text and the host-side shape caches (row pitches, plane geometry) are
+ *     per THREAD by design: ccvpe_last_error() reports the calling thread's last failure.
  */
 #ifndef CCVPE_HIP_H
 #define CCVPE_HIP_H
