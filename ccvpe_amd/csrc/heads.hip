@@ -351,6 +351,105 @@ __global__ __launch_bounds__(1024) void eval_post_kernel(const float* __restrict
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Eval metrics (train_KITTI.py:304-343, train_OxfordRobotCar.py:218-246, train_VIGOR.py:294-326): the reference's whole
+// per-sample loop body.  One workgroup per sample scans the heat-map and the ground-truth map together (first maximum of
+// each, ties to the smallest index, NaN skipped — eval_post_kernel's rule); thread 0 then does the scalar tail in DOUBLE,
+// because numpy does it in float64.  VEC: 16-byte loads (the launcher checks alignment and n % 4).
+// ---------------------------------------------------------------------------------------------
+struct ArgMax {
+  float v;
+  int i;
+  __device__ __forceinline__ void take(float ov, int oi) {       // oi > i always: a strict > keeps the first maximum
+    if (ov > v) { v = ov; i = oi; }
+  }
+  __device__ __forceinline__ void merge(float ov, int oi) {
+    if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
+  }
+};
+
+// degrees(acos(c)), reflected as Python's `math.degrees(-a) % 360` when the sine is negative: in [0, 360], where 360.0 is
+// what -a + 360 rounds to for a tiny positive a, in Python as here
+__device__ __forceinline__ double angle_deg_f64(double c, bool neg) {
+  const double a = acos(c) * (180.0 / 3.141592653589793);
+  if (!neg) return a;
+  const double m = fmod(-a, 360.0);
+  return m < 0.0 ? m + 360.0 : 0.0;                              // fmod(-0.0, 360) = -0.0 -> Python's % gives +0.0
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(1024) void eval_metrics_kernel(const float* __restrict__ heat, const float* __restrict__ ori,
+                                                            const float* __restrict__ gt, const float* __restrict__ gto,
+                                                            const double* __restrict__ heading,
+                                                            const double* __restrict__ mpp, double* __restrict__ rows,
+                                                            int h, int w) {
+  __shared__ float sv[2][16];
+  __shared__ int si[2][16];
+  const int n = h * w;
+  const size_t b = blockIdx.x;
+  const float* rh = heat + b * n;
+  const float* rg = gt + b * n;
+  ArgMax p = {-INFINITY, 0x7fffffff}, g = {-INFINITY, 0x7fffffff};
+  if (VEC) {
+    const int n4 = n >> 2;
+    for (int i = threadIdx.x; i < n4; i += blockDim.x) {
+      const cc_f32x4 a = reinterpret_cast<const cc_f32x4*>(rh)[i];
+      const cc_f32x4 c = reinterpret_cast<const cc_f32x4*>(rg)[i];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        p.take(a[k], 4 * i + k);
+        g.take(c[k], 4 * i + k);
+      }
+    }
+  } else {
+    for (int i = threadIdx.x; i < n; i += blockDim.x) {
+      p.take(rh[i], i);
+      g.take(rg[i], i);
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    p.merge(__shfl_xor(p.v, o, 64), __shfl_xor(p.i, o, 64));
+    g.merge(__shfl_xor(g.v, o, 64), __shfl_xor(g.i, o, 64));
+  }
+  if ((threadIdx.x & 63) == 0) {
+    sv[0][threadIdx.x >> 6] = p.v; si[0][threadIdx.x >> 6] = p.i;
+    sv[1][threadIdx.x >> 6] = g.v; si[1][threadIdx.x >> 6] = g.i;
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  for (int k = 1; k < (int)(blockDim.x >> 6); ++k) {
+    p.merge(sv[0][k], si[0][k]);
+    g.merge(sv[1][k], si[1][k]);
+  }
+  if (p.i == 0x7fffffff) p.i = 0;                                // nothing but NaN (or -inf): index 0, as eval_post_kernel
+  if (g.i == 0x7fffffff) g.i = 0;
+  const int py = p.i / w, px = p.i % w, gy = g.i / w, gx = g.i % w;
+  const int dy = gy - py, dx = gx - px;
+  const double m = mpp[b];
+  const double pd = sqrt((double)((long long)dy * dy + (long long)dx * dx));                       // train_KITTI.py:315
+  const double g2p = atan2(fabs((double)dx), fabs((double)dy)) * 180.0 / 3.141592653589793;         // :320 (atan2(0,0) = 0)
+  const double ad = fabs(heading[b] - g2p);                                                        // :321
+  const double rad = ad * 3.141592653589793 / 180.0;
+  const float c = ori[(b * 2 + 0) * n + p.i], s = ori[(b * 2 + 1) * n + p.i];
+  double ang = NAN, oe = NAN;
+  if (fabsf(c) <= 1.0f && fabsf(s) <= 1.0f) {                                                      // :331, in float32
+    ang = angle_deg_f64((double)c, s < 0.0f);
+    const float cg = gto[(b * 2 + 0) * n + g.i], sg = gto[(b * 2 + 1) * n + g.i];
+    const double d = fabs(angle_deg_f64(fmax(-1.0, fmin(1.0, (double)cg)), sg < 0.0f) - ang);
+    oe = fmin(d, 360.0 - d);                                                                       // :343
+  }
+  double* r = rows + b * 12;
+  r[0] = py; r[1] = px; r[2] = gy; r[3] = gx;
+  r[4] = pd;
+  r[5] = pd * m;                                                                                   // :317
+  r[6] = fabs(cos(rad) * pd) * m;                                                                  // :324,326
+  r[7] = fabs(sin(rad) * pd) * m;                                                                  // :325,327
+  r[8] = ang; r[9] = oe;
+  r[10] = (double)rh[p.i];
+  r[11] = (double)rh[g.i];                                                                         // train_VIGOR.py:326
+}
+
 // mode 0: -sum(num)/sum(den) ; mode 1: -sum(num)/B ; mode 2: +sum(num)/B
 // bf16 -> fp32 widening of an activation tensor (the bf16 storage path hands its last decoder levels to the fp32
 // kernels so that the heat-map arg-max keeps fp32 resolution: SURVEY.md section 7, "keep the last two levels in fp32")
@@ -445,6 +544,28 @@ extern "C" int ccvpe_eval_postprocess_f32(const float* heatmap, const float* ori
   if (B <= 0 || h <= 0 || w <= 0) return fail(CCVPE_EINVAL, "eval_postprocess: bad shape");
   hipLaunchKernelGGL(eval_post_kernel, dim3(B), dim3(1024), 0, (hipStream_t)stream, heatmap, ori, out, h, w);
   return check_launch("eval_post_kernel");
+}
+
+extern "C" int ccvpe_eval_metrics_f32(const float* heatmap, const float* ori, const float* gt, const float* gt_ori,
+                                      const double* heading_deg, const double* metres_per_pixel, double* rows, int B, int h,
+                                      int w, void* stream) {
+  if (B <= 0 || h <= 0 || w <= 0 || (long long)h * w > 0x7fffffffLL) return fail(CCVPE_EINVAL, "eval_metrics: bad shape");
+  if (!heatmap || !ori || !gt || !gt_ori || !heading_deg || !metres_per_pixel || !rows)
+    return fail(CCVPE_EINVAL, "eval_metrics: null pointer");
+  if ((reinterpret_cast<uintptr_t>(rows) | reinterpret_cast<uintptr_t>(heading_deg) |
+       reinterpret_cast<uintptr_t>(metres_per_pixel)) & 7)
+    return fail(CCVPE_EINVAL, "eval_metrics: rows, heading_deg and metres_per_pixel must be 8-byte aligned");
+  if ((reinterpret_cast<uintptr_t>(heatmap) | reinterpret_cast<uintptr_t>(ori) | reinterpret_cast<uintptr_t>(gt) |
+       reinterpret_cast<uintptr_t>(gt_ori)) & 3)
+    return fail(CCVPE_EINVAL, "eval_metrics: float maps must be 4-byte aligned");
+  const bool vec = (h * w) % 4 == 0 && aligned16(heatmap) && aligned16(gt);      // every row of both maps 16-byte aligned
+  if (vec)
+    hipLaunchKernelGGL(eval_metrics_kernel<true>, dim3(B), dim3(1024), 0, (hipStream_t)stream, heatmap, ori, gt, gt_ori,
+                       heading_deg, metres_per_pixel, rows, h, w);
+  else
+    hipLaunchKernelGGL(eval_metrics_kernel<false>, dim3(B), dim3(1024), 0, (hipStream_t)stream, heatmap, ori, gt, gt_ori,
+                       heading_deg, metres_per_pixel, rows, h, w);
+  return check_launch("eval_metrics_kernel");
 }
 
 extern "C" int ccvpe_infonce_scratch_floats(int B, int n) {

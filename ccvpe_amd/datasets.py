@@ -379,8 +379,10 @@ def pairs_is_training(pairs):
 
 class Batch(object):
     """One device batch: grd [B,3,h,w_fov], sat [B,3,H,W] (normalised fp32), angle_deg [B], center [B,2], cities, indices and —
-    with targets — gt [B,1,H,W], gt_flat [B,H*W], gt_ori [B,2,H,W], labels (six max-pooled orientation-binned maps)."""
-    __slots__ = ("grd", "sat", "angle_deg", "center", "cities", "indices", "gt", "gt_flat", "gt_ori", "labels")
+    with targets — gt [B,1,H,W], gt_flat [B,H*W], gt_ori [B,2,H,W], labels (six max-pooled orientation-binned maps).
+    heading_deg [B] is the samples' angle_deg again as FLOAT64, unwrapped: the loaders' `orientation_angle`, a Python float
+    that the reference's test loops use at full precision (ccvpe_amd.evaluate.evaluate_batches)."""
+    __slots__ = ("grd", "sat", "angle_deg", "heading_deg", "center", "cities", "indices", "gt", "gt_flat", "gt_ori", "labels")
 
 
 class DeviceBatches(object):
@@ -461,6 +463,7 @@ class DeviceBatches(object):
             preprocess.preprocess(g, self.grd_hw, dst=out.grd[i], roll=s["roll"], keep_w=self.keep_w)
             preprocess.preprocess(a, self.sat_hw, dst=out.sat[i])
         out.angle_deg = torch.tensor([s["angle_deg"] for s in samples], device=dev, dtype=torch.float32)
+        out.heading_deg = torch.tensor([s["angle_deg"] for s in samples], device=dev, dtype=torch.float64)
         out.center = torch.tensor([s["center"] for s in samples], device=dev, dtype=torch.float32)
         out.cities = [s["city"] for s in samples]
         out.indices = [s["index"] for s in samples]

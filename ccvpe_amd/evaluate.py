@@ -13,6 +13,12 @@ train_KITTI.py:283-380), MI355X-style:
 
 `forward_fn(grd, sat)` returns the 9-tuple; `postprocess_fn(heatmap, ori)` returns [B,6]
 (y, x, cos, sin, angle_deg, prob) — ccvpe_amd.ops.eval_postprocess on the GPU.
+
+The reference's full TEST PROTOCOLS (longitudinal / lateral error, recall under 1 / 3 / 5 m and degrees, probability at the
+ground truth, Oxford's three traversals) are the second half of this file: `evaluate_batches` drives a
+`datasets.DeviceBatches` through the forward and ccvpe_eval_metrics_f32 (twelve doubles per sample, `metrics_spec` is its
+numpy specification), reads ONE table back after the loop, and `summarise` / `format_report` produce what the three test
+scripts print.
 """
 import math
 
@@ -42,6 +48,25 @@ def sample_metrics(post_row, gt_yx, gt_cos_sin, metres_per_pixel):
     return pd, md, oe, prob
 
 
+def _gather_rows(local, nmax, device=None):
+    """All ranks' rows ordered by their first column (the sample index, >= 0).  local: [m, C] float64 on the host, m <= nmax on
+    every rank: shards are padded to nmax rows with index -1, gathered (RCCL on GPUs, gloo on the CPU) and the padding dropped."""
+    distributed = dist.is_available() and dist.is_initialized()
+    world = dist.get_world_size() if distributed else 1
+    if distributed and world > 1:
+        buf = torch.full((nmax, local.shape[1]), -1.0, dtype=torch.float64)
+        buf[:local.shape[0]] = local
+        if device is not None and dist.get_backend() == "nccl":
+            buf = buf.to(device)
+        gathered = [torch.empty_like(buf) for _ in range(world)]
+        dist.all_gather(gathered, buf)
+        allrows = torch.cat([g.cpu() for g in gathered])
+        allrows = allrows[allrows[:, 0] >= 0]
+    else:
+        allrows = local
+    return allrows[allrows[:, 0].argsort()]
+
+
 def evaluate(forward_fn, postprocess_fn, samples, batch_size, device=None):
     """samples: sequence of dicts with keys grd [3,h,w], sat [3,512,512], gt_yx (y,x), gt_cos_sin,
     metres_per_pixel.  Returns (on every rank) a dict of global statistics + the gathered rows
@@ -63,20 +88,8 @@ def evaluate(forward_fn, postprocess_fn, samples, batch_size, device=None):
             s = samples[j]
             rows.append((j,) + sample_metrics(post[k], s["gt_yx"], s["gt_cos_sin"], s["metres_per_pixel"]))
     local = torch.tensor(rows, dtype=torch.float64).reshape(-1, 5)
-    if distributed and world > 1:
-        # shards differ by at most one sample: pad to the common length, gather, drop the padding
-        nmax = (len(samples) + world - 1) // world
-        buf = torch.full((nmax, 5), -1.0, dtype=torch.float64)
-        buf[:local.shape[0]] = local
-        if device is not None and dist.get_backend() == "nccl":
-            buf = buf.to(device)
-        gathered = [torch.empty_like(buf) for _ in range(world)]
-        dist.all_gather(gathered, buf)
-        allrows = torch.cat([g.cpu() for g in gathered])
-        allrows = allrows[allrows[:, 0] >= 0]
-    else:
-        allrows = local
-    allrows = allrows[allrows[:, 0].argsort()]
+    # shards differ by at most one sample: the common padded length
+    allrows = _gather_rows(local, (len(samples) + world - 1) // world, device)
     res = allrows[:, 1:].numpy()
     oe = res[:, 2][~np.isnan(res[:, 2])]
     return {
@@ -88,3 +101,213 @@ def evaluate(forward_fn, postprocess_fn, samples, batch_size, device=None):
         "mean_probability": float(np.mean(res[:, 3])),
         "rows": res,
     }
+
+
+# ---- the reference test protocols: twelve numbers per sample, the reports of the three test scripts ---------------------
+# columns of a metric row (ccvpe_eval_metrics_f32 / metrics_spec)
+PRED_Y, PRED_X, GT_Y, GT_X, PIXEL, METRE, LONGITUDINAL, LATERAL, ANGLE, ORIENTATION, PROB, PROB_AT_GT = range(12)
+THRESHOLDS = (1, 3, 5)
+# ground resolution of the 512 x 512 aerial inputs, metres per pixel (train_VIGOR.py:300-307, train_OxfordRobotCar.py:204,249)
+VIGOR_METRES_PER_PIXEL = {"NewYork": 0.113248 / 512 * 640, "Seattle": 0.100817 / 512 * 640,
+                          "SanFrancisco": 0.118141 / 512 * 640, "Chicago": 0.111262 / 512 * 640}
+OXFORD_METRES_PER_PIXEL = 0.09240351462361521 / 512 * 800
+
+
+def metrics_spec(heatmap, ori, gt, gt_ori, heading_deg, metres_per_pixel):
+    """The specification of ccvpe_eval_metrics_f32: the per-sample body of the reference's test loops (train_KITTI.py:309-343,
+    train_OxfordRobotCar.py:218-246, train_VIGOR.py:294-326) in numpy float64, one sample at a time.  heatmap, gt [B,1,h,w] and
+    ori, gt_ori [B,2,h,w] float32 (arrays or host tensors), heading_deg and metres_per_pixel [B] -> [B,12] float64."""
+    heatmap, ori, gt, gt_ori = (np.asarray(t, dtype=np.float32) for t in (heatmap, ori, gt, gt_ori))
+    heading_deg = np.asarray(heading_deg, dtype=np.float64).reshape(-1)
+    metres_per_pixel = np.asarray(metres_per_pixel, dtype=np.float64).reshape(-1)
+    rows = np.full((heatmap.shape[0], 12), np.nan, dtype=np.float64)
+    n, w = heatmap.shape[2] * heatmap.shape[3], heatmap.shape[3]
+    for b in range(heatmap.shape[0]):
+        kp, kg = int(np.argmax(heatmap[b].reshape(n))), int(np.argmax(gt[b].reshape(n)))      # first maxima, row-major
+        (py, px), (gy, gx) = divmod(kp, w), divmod(kg, w)
+        dy, dx = gy - py, gx - px
+        pixel = np.sqrt(np.float64(dy * dy + dx * dx))
+        bearing = np.arctan2(np.float64(abs(dx)), np.float64(abs(dy))) * 180 / math.pi        # GT -> prediction, atan2(0, 0) = 0
+        turn = np.abs(heading_deg[b] - bearing) * np.pi / 180                                  # heading as given: no wrap
+        r = rows[b]
+        r[PRED_Y], r[PRED_X], r[GT_Y], r[GT_X] = py, px, gy, gx
+        r[PIXEL], r[METRE] = pixel, pixel * metres_per_pixel[b]
+        r[LONGITUDINAL] = np.abs(np.cos(turn) * pixel) * metres_per_pixel[b]
+        r[LATERAL] = np.abs(np.sin(turn) * pixel) * metres_per_pixel[b]
+        c, s = ori[b, 0, py, px], ori[b, 1, py, px]
+        if np.abs(c) <= 1 and np.abs(s) <= 1:                        # float32 comparisons, as the reference's
+            up = math.degrees(math.acos(c))
+            r[ANGLE] = (-up) % 360 if s < 0 else up
+            d = abs(_angle_from_cos_sin(float(gt_ori[b, 0, gy, gx]), float(gt_ori[b, 1, gy, gx])) - r[ANGLE])
+            r[ORIENTATION] = min(d, 360 - d)
+        r[PROB], r[PROB_AT_GT] = heatmap[b, 0, py, px], heatmap[b, 0, gy, gx]
+    return rows
+
+
+def _mean(x):
+    return float(np.mean(x)) if len(x) else float("nan")
+
+
+def _median(x):
+    return float(np.median(x)) if len(x) else float("nan")
+
+
+def _within(x):
+    return {t: float(np.sum(x < t) / len(x)) if len(x) else float("nan") for t in THRESHOLDS}
+
+
+def _summarise_one(rows):
+    # the probabilities are float32 values; the reference averages its list of them in float32 and prints a float32
+    p_gt, p_max = rows[:, PROB_AT_GT].astype(np.float32), rows[:, PROB].astype(np.float32)
+    oe = rows[:, ORIENTATION]
+    oe = oe[~np.isnan(oe)]                                           # the reference appends to this list only when |cos|,|sin| <= 1
+    out = {"n": int(rows.shape[0])}
+    for name, x in (("pixel_error", rows[:, PIXEL]), ("metre_error", rows[:, METRE]),
+                    ("longitudinal_error", rows[:, LONGITUDINAL]), ("lateral_error", rows[:, LATERAL]),
+                    ("orientation_error", oe), ("probability_at_gt", p_gt), ("probability", p_max)):
+        out["mean_" + name], out["median_" + name] = _mean(x), _median(x)
+    out["lateral_within"] = _within(rows[:, LATERAL])
+    out["longitudinal_within"] = _within(rows[:, LONGITUDINAL])
+    out["orientation_within"] = _within(oe)
+    return out
+
+
+def summarise(rows, sets=None):
+    """The quantities the reference's test scripts print, from [n,12] metric rows: n, mean_/median_ of pixel_error, metre_error,
+    longitudinal_error, lateral_error, orientation_error (non-NaN entries only), probability_at_gt and probability (at the
+    arg-max; these two are taken in float32 as the reference takes them, and returned widened), and lateral_within / longitudinal_within / orientation_within = {1: , 3: , 5: } as sum(x < t) / len(x).
+    sets: ordered mapping name -> row positions (index array, slice or boolean mask); the same statistics per set are under
+    "sets"."""
+    rows = np.asarray(rows, dtype=np.float64).reshape(-1, 12)
+    out = _summarise_one(rows)
+    if sets:
+        out["sets"] = {name: _summarise_one(rows[sel]) for name, sel in sets.items()}
+    return out
+
+
+def _three(d):
+    return " ".join(str(d[t]) for t in THRESHOLDS)
+
+
+def _report_kitti(s, title):
+    bar = "-" * 39
+    return ([bar] + ([title] if title else []) +
+            ["mean localization error (m):  %s" % s["mean_metre_error"],
+             "median localization error (m):  %s" % s["median_metre_error"], bar,
+             "mean orientation error (degrees):  %s" % s["mean_orientation_error"],
+             "median orientation error (degrees):  %s" % s["median_orientation_error"], bar,
+             "percentage of samples with lateral localization error under 1m, 3m, and 5m:  " + _three(s["lateral_within"]),
+             "percentage of samples with longitudinal localization error under 1m, 3m, and 5m:  " + _three(s["longitudinal_within"]),
+             "percentage of samples with orientation error under 1 degree, 3 degrees, and 5 degrees:  " + _three(s["orientation_within"])])
+
+
+def _report_oxford(s, title):
+    return (([title] if title else []) +
+            ["mean error (m):  %s" % s["mean_metre_error"], "median error (m):  %s" % s["median_metre_error"],
+             "mean longitudinal error (m):  %s" % s["mean_longitudinal_error"],
+             "median longitudinal error (m):  %s" % s["median_longitudinal_error"],
+             "mean lateral error (m):  %s" % s["mean_lateral_error"], "median lateral error (m):  %s" % s["median_lateral_error"],
+             "mean orientation error (deg):  %s" % s["mean_orientation_error"],
+             "median orientation error (deg):  %s" % s["median_orientation_error"],
+             "percentage of samples with longitudinal localization error under 1m, 3m, and 5m:  " + _three(s["longitudinal_within"]),
+             "percentage of samples with lateral localization error under 1m, 3m, and 5m:  " + _three(s["lateral_within"]),
+             "percentage of samples with orientation error under 1 degree, 3 degrees, and 5 degrees:  " + _three(s["orientation_within"])])
+
+
+def format_report(summary, kind):
+    """The lines the reference's test script of `kind` prints ('vigor': train_VIGOR.py:329-338, 'kitti': train_KITTI.py:345-360,
+    'oxford': train_OxfordRobotCar.py:248-268), as one string.  KITTI and Oxford report set by set when the summary has sets,
+    each under its name, and the whole run otherwise.  Where this departs from the scripts: the title line of a block
+    ('Test 1 set', 'test1') is the SET's name, so a summary without sets prints no title — pass sets={"Test 1 set": ...} to
+    summarise / evaluate_batches for KITTI's; and Oxford's mean / median error is taken over metres per sample, where the script
+    scales the mean pixel distance afterwards (the last place may differ).  The probabilities print as the float32 values they
+    are, like the script's."""
+    if kind == "vigor":
+        bar = "-" * 39
+        lines = ["mean localization error (m):  %s" % summary["mean_metre_error"],
+                 "median localization error (m):  %s" % summary["median_metre_error"], bar,
+                 "mean orientation error (degrees):  %s" % summary["mean_orientation_error"],
+                 "median orientation error (degrees):  %s" % summary["median_orientation_error"], bar,
+                 "mean probability at gt %s" % np.float32(summary["mean_probability_at_gt"]),
+                 "median probability at gt %s" % np.float32(summary["median_probability_at_gt"])]
+    elif kind in ("kitti", "oxford"):
+        blocks = list(summary["sets"].items()) if summary.get("sets") else [(None, summary)]
+        one = _report_kitti if kind == "kitti" else _report_oxford
+        lines = []
+        for k, (title, s) in enumerate(blocks):
+            if kind == "oxford" and k:
+                lines.append("-" * 70)
+            lines += one(s, title)
+    else:
+        raise ValueError("kind must be 'vigor', 'kitti' or 'oxford'")
+    return "\n".join(lines)
+
+
+def default_metres_per_pixel(pairs):
+    """The ground resolution the reference's test script uses for `pairs`: a float (KITTI, Oxford) or the per-city table
+    (VIGOR)."""
+    from . import datasets
+    if isinstance(pairs, datasets.KITTIPairs):
+        return float(pairs.meter_per_pixel)                                     # train_KITTI.py:317
+    if isinstance(pairs, datasets.OxfordPairs):
+        return OXFORD_METRES_PER_PIXEL
+    if isinstance(pairs, datasets.VIGORPairs):
+        return VIGOR_METRES_PER_PIXEL
+    raise ValueError("no default metres_per_pixel for %s: pass a float or a {city: float} table" % type(pairs).__name__)
+
+
+def default_sets(pairs):
+    """name -> sample indices: test1 / test2 / test3 of an Oxford test split (its three traversals, reported one by one,
+    train_OxfordRobotCar.py:209-400); None — one set — otherwise."""
+    from . import datasets
+    if isinstance(pairs, datasets.OxfordPairs) and pairs.split == "test":
+        ends = np.cumsum(pairs.list_lengths)
+        return {"test%d" % (k + 1): np.arange(e - n, e) for k, (n, e) in enumerate(zip(pairs.list_lengths, ends))}
+    return None
+
+
+def evaluate_batches(forward_fn, batches, metres_per_pixel=None, sets=None):
+    """The reference's test protocol over a `datasets.DeviceBatches` built with targets=True: per batch the forward (no_grad) and
+    ONE ccvpe_eval_metrics_f32 launch that writes the batch's rows into a device table [n,12]; nothing is copied to the host
+    inside the loop — the table is read back once after it, gathered over the ranks (each rank iterates its own shard of
+    `batches`) and ordered by sample index.  metres_per_pixel: a float, a {city: float} table looked up through batch.cities, or
+    None = default_metres_per_pixel(batches.pairs).  sets: name -> sample indices, None = default_sets(batches.pairs).
+    Returns summarise(...) + "rows" [n,12] + "indices" [n] on every rank."""
+    from . import ops
+    if not batches.targets:
+        raise ValueError("evaluate_batches needs DeviceBatches(..., targets=True): the ground truth comes from the batch")
+    world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
+    if world > 1 and batches.shard != "exact":
+        raise ValueError("evaluate_batches needs DeviceBatches(..., shard='exact') on several ranks: a '%s' shard repeats or drops "
+                         "samples, and the gathered statistics would count them wrongly" % batches.shard)
+    mpp = default_metres_per_pixel(batches.pairs) if metres_per_pixel is None else metres_per_pixel
+    if sets is None:
+        sets = default_sets(batches.pairs)
+    dev = batches.device
+    n_local = len(batches.indices)
+    table = torch.empty((n_local, 12), device=dev, dtype=torch.float64)
+    if not isinstance(mpp, dict):
+        mpp_const = torch.full((max(1, batches.batch_size),), float(mpp), device=dev, dtype=torch.float64)
+    indices, k = [], 0
+    for batch in batches:
+        b = len(batch.indices)
+        with torch.no_grad():
+            out = forward_fn(batch.grd, batch.sat)
+        m = (torch.tensor([mpp[c] for c in batch.cities], device=dev, dtype=torch.float64) if isinstance(mpp, dict)
+             else mpp_const[:b])
+        ops.eval_metrics(out[1], out[2], batch.gt, batch.gt_ori, batch.heading_deg, m, out=table[k:k + b])
+        indices += [int(i) for i in batch.indices]
+        k += b
+    host = table[:k].cpu()                                                       # the one read-back (and the one sync)
+    local = torch.cat([torch.tensor(indices, dtype=torch.float64).reshape(-1, 1), host], dim=1)
+    nmax = local.shape[0]
+    if world > 1:
+        t = torch.tensor([nmax], dtype=torch.int64, device=dev if dist.get_backend() == "nccl" else "cpu")
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)                                 # shards may differ in length
+        nmax = int(t.item())
+    allrows = _gather_rows(local, nmax, dev).numpy()
+    idx, rows = allrows[:, 0].astype(np.int64), allrows[:, 1:]
+    masks = {name: np.isin(idx, np.asarray(sel)) for name, sel in sets.items()} if sets else None
+    res = summarise(rows, masks)
+    res["rows"], res["indices"] = rows, idx
+    return res

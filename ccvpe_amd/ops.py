@@ -756,6 +756,30 @@ def eval_postprocess(heatmap, ori):
     return out
 
 
+def eval_metrics(heatmap, ori, gt, gt_ori, heading_deg, metres_per_pixel, out=None):
+    """The reference test protocols' per-sample loop body on the device (train_KITTI.py:304-343, train_VIGOR.py:294-326):
+    returns [B,12] float64 = (pred_y, pred_x, gt_y, gt_x, pixel distance, metres, longitudinal metres, lateral metres,
+    predicted angle, orientation error, heatmap[pred], heatmap[gt]) — ccvpe_amd.evaluate.metrics_spec is the specification.
+    heading_deg, metres_per_pixel: [B] float64 device tensors.  out: a caller's [B,12] float64 slice of a larger table."""
+    lib = _lib.load()
+    for t, nm in ((heatmap, "heatmap"), (ori, "ori"), (gt, "gt"), (gt_ori, "gt_ori")):
+        _chk(t, nm)
+    for t, nm in ((heading_deg, "heading_deg"), (metres_per_pixel, "metres_per_pixel"), (out, "out")):
+        _chk(t, nm, torch.float64)
+    b, _, h, w = heatmap.shape
+    if ori.shape != (b, 2, h, w) or gt.shape != heatmap.shape or gt_ori.shape != ori.shape:
+        raise ValueError("eval_metrics: heatmap/gt [B,1,h,w] and ori/gt_ori [B,2,h,w] expected")
+    if heading_deg.numel() != b or metres_per_pixel.numel() != b:
+        raise ValueError("eval_metrics: heading_deg and metres_per_pixel must hold one value per sample")
+    if out is None:
+        out = _empty((b, 12), device=heatmap.device, dtype=torch.float64)
+    elif tuple(out.shape) != (b, 12):
+        raise ValueError("eval_metrics: out must be [%d,12], got %s" % (b, tuple(out.shape)))
+    check(lib.ccvpe_eval_metrics_f32(_ptr(heatmap), _ptr(ori), _ptr(gt), _ptr(gt_ori), _ptr(heading_deg),
+                                     _ptr(metres_per_pixel), _ptr(out), b, h, w, _stream()), "ccvpe_eval_metrics_f32")
+    return out
+
+
 def _loss_common(fn, name, tensors, extra):
     lib = _lib.load()
     for i, t in enumerate(tensors):

@@ -401,6 +401,26 @@ int ccvpe_eval_postprocess_f32(const float* heatmap, const float* ori, float* ou
                                void* stream);
 
 /* -------------------------------------------------------------------------------------------
+ * The reference test protocols' whole per-sample loop body in one launch (train_KITTI.py:304-343,
+ * train_OxfordRobotCar.py:218-246, train_VIGOR.py:294-326): first-maximum arg-max of the heat-map AND of
+ * the ground-truth map (ties to the smallest index, as numpy.argmax), then in double precision
+ *   rows[b] = { pred_y, pred_x, gt_y, gt_x,
+ *               pixel distance, metres (= distance * metres_per_pixel[b]),
+ *               longitudinal metres = |cos(angle_diff * pi / 180) * distance| * metres_per_pixel[b],
+ *               lateral metres      = |sin(angle_diff * pi / 180) * distance| * metres_per_pixel[b],
+ *               predicted angle in degrees (NaN if |cos| > 1 or |sin| > 1 at the arg-max, compared in float),
+ *               orientation error min(|d|, 360 - |d|) against the angle of gt_ori at the GT arg-max (NaN likewise),
+ *               heatmap[pred], heatmap[gt] }
+ * with angle_diff = |heading_deg[b] - atan2(|gt_x - pred_x|, |gt_y - pred_y|) * 180 / pi|; heading_deg is used as
+ * given (no wrap).  heatmap, gt [B,h*w]; ori, gt_ori [B,2,h*w] (NCHW); heading_deg, metres_per_pixel [B] doubles;
+ * rows [B,12] doubles, 8-byte aligned — any row of a larger table.  16-byte loads when h*w % 4 == 0 and both maps
+ * are 16-byte aligned, scalar loads otherwise.
+ * ----------------------------------------------------------------------------------------- */
+int ccvpe_eval_metrics_f32(const float* heatmap, const float* ori, const float* gt, const float* gt_ori,
+                           const double* heading_deg, const double* metres_per_pixel, double* rows, int batch, int h,
+                           int w, void* stream);
+
+/* -------------------------------------------------------------------------------------------
  * Losses (losses.py:4-29), device scalars out.  `acc` is caller-provided scratch.
  *   infoNCE: accumulates num = sum_{label>1e-2} log(softmax(s/T))*label and den = sum label over
  *            the whole batch; loss = -num/den.            scores/labels [B,n]
