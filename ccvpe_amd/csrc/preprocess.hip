@@ -73,6 +73,69 @@ __global__ __launch_bounds__(256) void resample_v_norm_kernel(const unsigned cha
   dst[2 * plane + idx] = ((float)clip8(s2) / 255.0f - m2) / d2;
 }
 
+// vertical pass alone, for the device image cache: tmp [H][wo][3] u8 -> dst [ho][wo][3] u8, full width, no roll.  One lane
+// per output BYTE: a row of tmp and a row of dst are both wo * 3 contiguous bytes, so loads and stores coalesce.
+__global__ __launch_bounds__(256) void resample_v_u8_kernel(const unsigned char* __restrict__ tmp, int wo,
+                                                            const int* __restrict__ bounds, const int* __restrict__ kk,
+                                                            int ksize, unsigned char* __restrict__ dst, int ho) {
+  const long pitch = (long)wo * 3;
+  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (long)ho * pitch) return;
+  const int yy = (int)(idx / pitch);
+  const long xc = idx - (long)yy * pitch;
+  const int ymin = bounds[2 * yy], yn = bounds[2 * yy + 1];
+  const int* k = kk + (size_t)yy * ksize;
+  int s = 1 << (PRECISION_BITS - 1);
+  const unsigned char* col = tmp + (size_t)ymin * pitch + xc;
+  for (int y = 0; y < yn; ++y) s += col[(size_t)y * pitch] * k[y];
+  dst[idx] = clip8(s);
+}
+
+// Batch assembly from the device image cache: srcs[b] = device address of a resized [h][w][3] u8 image,
+//   dst[b][c][y][x] = ((float)src_b[y][(x - roll_b) mod w][c] / 255 - mean[c]) / std[c],   x < keep
+// — the ToTensor / Normalize arithmetic of resample_v_norm_kernel, operation for operation (two IEEE divisions, nothing to
+// contract).  Pure streaming: 3 B read, 12 B written per pixel.  blockIdx.y = sample.
+// VEC: a lane owns four consecutive output columns of one row (keep % 4 == 0, so a group never straddles rows and every
+// plane row is 16-byte aligned) and writes one 16-byte store per channel plane, lanes along x.  The source bytes are read
+// per lane, one byte load each: the roll shifts the source by an arbitrary number of 3-byte pixels, so no wider load is
+// aligned, and neighbouring lanes read neighbouring 12-byte runs of the same cache lines.  The wrap
+// can fall INSIDE a group, so the modulo is taken per element.
+template <bool VEC>
+__global__ __launch_bounds__(256) void gather_norm_kernel(const long long* __restrict__ srcs, const int* __restrict__ rolls,
+                                                          int h, int w, int keep, float* __restrict__ dst, float m0, float m1,
+                                                          float m2, float d0, float d1, float d2) {
+  constexpr int NX = VEC ? 4 : 1;
+  const int per_row = keep / NX;
+  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (long)h * per_row) return;
+  const int b = blockIdx.y;
+  const int y = (int)(idx / per_row), x0 = (int)(idx - (long)y * per_row) * NX;
+  int r = rolls[b] % w;                        // torch.roll(x, r, W): out[..., j] = in[..., (j - r) mod W]
+  if (r < 0) r += w;
+  const unsigned char* row = reinterpret_cast<const unsigned char*>(srcs[b]) + (size_t)y * w * 3;
+  float v0[NX], v1[NX], v2[NX];
+#pragma unroll
+  for (int j = 0; j < NX; ++j) {
+    int xs = x0 + j - r;                       // x0 + j < keep <= w and 0 <= r < w: -w < xs < w
+    if (xs < 0) xs += w;
+    const unsigned char* p = row + (size_t)xs * 3;
+    v0[j] = ((float)p[0] / 255.0f - m0) / d0;
+    v1[j] = ((float)p[1] / 255.0f - m1) / d1;
+    v2[j] = ((float)p[2] / 255.0f - m2) / d2;
+  }
+  const size_t plane = (size_t)h * keep;
+  float* o = dst + (size_t)b * 3 * plane + (size_t)y * keep + x0;
+  if constexpr (VEC) {
+    *reinterpret_cast<cc_f32x4*>(o) = (cc_f32x4){v0[0], v0[1], v0[2], v0[3]};
+    *reinterpret_cast<cc_f32x4*>(o + plane) = (cc_f32x4){v1[0], v1[1], v1[2], v1[3]};
+    *reinterpret_cast<cc_f32x4*>(o + 2 * plane) = (cc_f32x4){v2[0], v2[1], v2[2], v2[3]};
+  } else {
+    o[0] = v0[0];
+    o[plane] = v1[0];
+    o[2 * plane] = v2[0];
+  }
+}
+
 }  // namespace ccvpe
 
 using namespace ccvpe;
@@ -92,4 +155,39 @@ extern "C" int ccvpe_preprocess_u8_f32(const unsigned char* src, int in_h, int i
   hipLaunchKernelGGL(resample_v_norm_kernel, dim3((unsigned)((n2 + 255) / 256)), dim3(256), 0, st, tmp, out_w, ybounds, ycoef, yksize,
                      dst, out_h, keep_w, roll, mean[0], mean[1], mean[2], stdv[0], stdv[1], stdv[2]);
   return check_launch("preprocess");
+}
+
+extern "C" int ccvpe_resize_u8(const unsigned char* src, int in_h, int in_w, const int* xbounds, const int* xcoef, int xksize,
+                               const int* ybounds, const int* ycoef, int yksize, unsigned char* tmp, unsigned char* dst_u8,
+                               int out_h, int out_w, void* stream) {
+  if (in_h <= 0 || in_w <= 0 || out_h <= 0 || out_w <= 0 || xksize <= 0 || yksize <= 0) return fail(CCVPE_EINVAL, "resize_u8: bad shape");
+  if (!src || !tmp || !dst_u8 || !xbounds || !xcoef || !ybounds || !ycoef) return fail(CCVPE_EINVAL, "resize_u8: null pointer");
+  hipStream_t st = (hipStream_t)stream;
+  const long n1 = (long)in_h * out_w;
+  hipLaunchKernelGGL(resample_h_kernel, dim3((unsigned)((n1 + 255) / 256)), dim3(256), 0, st, src, in_h, in_w, xbounds, xcoef, xksize,
+                     tmp, out_w);
+  const long n2 = (long)out_h * out_w * 3;
+  hipLaunchKernelGGL(resample_v_u8_kernel, dim3((unsigned)((n2 + 255) / 256)), dim3(256), 0, st, tmp, out_w, ybounds, ycoef, yksize,
+                     dst_u8, out_h);
+  return check_launch("resize_u8");
+}
+
+extern "C" int ccvpe_gather_norm_u8_f32(const long long* srcs, const int* rolls, int batch, int h, int w, int keep_w,
+                                        const float* mean, const float* stdv, float* dst, void* stream) {
+  if (batch < 0 || batch > 65535 || h <= 0 || w <= 0 || keep_w <= 0 || keep_w > w) return fail(CCVPE_EINVAL, "gather_norm: bad shape");
+  if ((long)h * w * 3 > 0x7fffffffL) return fail(CCVPE_EINVAL, "gather_norm: image above 2 GB");
+  if (!mean || !stdv) return fail(CCVPE_EINVAL, "gather_norm: null pointer");
+  if (batch == 0) return CCVPE_OK;                       // an empty batch has empty (possibly null) tables and nothing to write
+  if (!srcs || !rolls || !dst) return fail(CCVPE_EINVAL, "gather_norm: null pointer");
+  hipStream_t st = (hipStream_t)stream;
+  if (keep_w % 4 == 0 && aligned16(dst)) {
+    const long n = (long)h * (keep_w / 4);
+    hipLaunchKernelGGL((gather_norm_kernel<true>), dim3((unsigned)((n + 255) / 256), (unsigned)batch), dim3(256), 0, st, srcs, rolls, h, w,
+                       keep_w, dst, mean[0], mean[1], mean[2], stdv[0], stdv[1], stdv[2]);
+  } else {
+    const long n = (long)h * keep_w;
+    hipLaunchKernelGGL((gather_norm_kernel<false>), dim3((unsigned)((n + 255) / 256), (unsigned)batch), dim3(256), 0, st, srcs, rolls, h, w,
+                       keep_w, dst, mean[0], mean[1], mean[2], stdv[0], stdv[1], stdv[2]);
+  }
+  return check_launch("gather_norm");
 }

@@ -133,26 +133,44 @@ class VIGORPairs(object):
         and hands the result to sample(draws=...), so a seeded iteration is reproducible whatever the decode threads do."""
         return self.rotation_fraction(idx), self.positive(idx)
 
-    def sample(self, idx, sat_hw=(512, 512), grd_hw=(320, 640), draws=None):
+    def keys(self, idx, draws):
+        """Source files of sample idx under `draws` (a draw() result), for a device image cache: the panorama's path and the
+        path of the aerial tile the draw selected."""
+        return {"grd": self.grd_paths[idx], "sat": self.sat_paths[self.labels[idx, draws[1][0]]]}
+
+    def sample(self, idx, sat_hw=(512, 512), grd_hw=(320, 640), draws=None, cached=None):
         """Decode sample idx.  Returns a dict: grd_u8 / sat_u8 (HWC uint8 numpy, as PIL decodes them), roll (pixels of the
         RESIZED panorama, datasets.py:121), angle_deg, center (cx, cy) of the Gaussian on the resized aerial grid
-        (cx = column offset, cy = -row offset, both rescaled and rounded as datasets.py:141-142 does), city."""
+        (cx = column offset, cy = -row offset, both rescaled and rounded as datasets.py:141-142 does), city.
+        cached: {side: raw (h, w)} of the sides a device image cache already holds — such a side is not opened or decoded and
+        its *_u8 entry is None (`center` takes the raw tile size from the mapping); every other key is as without it.  With
+        a mapping (even an empty one) an unreadable panorama's blank image is marked `nocache=("grd",)`."""
         from PIL import Image
-        try:
-            with Image.open(self.grd_paths[idx]) as im:
-                grd = np.array(im.convert("RGB"))             # owning, writable: torch.from_numpy needs that
-        except (OSError, ValueError):                                  # unreadable panorama -> blank image (datasets.py:103-105)
-            grd = np.zeros((grd_hw[0], grd_hw[1], 3), dtype=np.uint8)
+        mark = {}
+        if cached is not None and "grd" in cached:
+            grd = None
+        else:
+            try:
+                with Image.open(self.grd_paths[idx]) as im:
+                    grd = np.array(im.convert("RGB"))             # owning, writable: torch.from_numpy needs that
+            except (OSError, ValueError):                                  # unreadable panorama -> blank image (datasets.py:103-105)
+                grd = np.zeros((grd_hw[0], grd_hw[1], 3), dtype=np.uint8)
+                if cached is not None:
+                    mark = {"nocache": ("grd",)}
         rot, (k, drow, dcol) = self.draw(idx) if draws is None else draws
-        with Image.open(self.sat_paths[self.labels[idx, k]]) as im:
-            sat = np.array(im.convert("RGB"))
-        h_raw, w_raw = sat.shape[0], sat.shape[1]
+        if cached is not None and "sat" in cached:
+            sat = None
+            h_raw, w_raw = cached["sat"]
+        else:
+            with Image.open(self.sat_paths[self.labels[idx, k]]) as im:
+                sat = np.array(im.convert("RGB"))
+            h_raw, w_raw = sat.shape[0], sat.shape[1]
         row = np.round(drow / h_raw * sat_hw[0])
         col = np.round(dcol / w_raw * sat_hw[1])
         # torch.round (half to even) of rotation * width, like datasets.py:121
         roll = int(torch.round(torch.as_tensor(rot) * grd_hw[1]).int().item())
         return dict(grd_u8=grd, sat_u8=sat, roll=roll, angle_deg=rot * 360.0,
-                    center=(float(col), float(-row)), city=self.city_of[idx], index=int(idx))
+                    center=(float(col), float(-row)), city=self.city_of[idx], index=int(idx), **mark)
 
 
 # ---- KITTI (datasets.py:354-372: constants of the reference's loader) ---------------------------------------------------
@@ -215,11 +233,18 @@ class KITTIPairs(object):
         """The sample's random choices (see VIGORPairs.draw)."""
         return self.perturbation(idx)
 
-    def sample(self, idx, sat_hw=(512, 512), grd_hw=(256, 1024), draws=None):
+    def keys(self, idx, draws):
+        """Source files of sample idx for a device image cache: the camera image; the aerial side is None — the aligned crop
+        depends on the sample's draw (both device_align modes keep their path)."""
+        name = self.lines[idx].split(" ")[0] if self.test else self.lines[idx]
+        return {"grd": self.paths(name)[2], "sat": None}
+
+    def sample(self, idx, sat_hw=(512, 512), grd_hw=(256, 1024), draws=None, cached=None):
         """Decode + align sample idx.  Returns the dict DeviceBatches consumes: grd_u8 (the left camera image as decoded),
         sat_u8 (the aligned, perturbed 512 x 512 aerial crop; device_align: sat_src_u8 and align in its place), roll = 0, angle_deg
         (orientation ground truth in [0, 360]),
-        center = (x_offset, y_offset) of the Gaussian (datasets.py:475-476), city = the drive, index."""
+        center = (x_offset, y_offset) of the Gaussian (datasets.py:475-476), city = the drive, index.
+        cached: {"grd": raw (h, w)} when a device image cache holds the camera image — it is then not opened, grd_u8 is None."""
         from PIL import Image
         name = self.lines[idx].split(" ")[0] if self.test else self.lines[idx]
         sat_path, oxts_path, grd_path = self.paths(name)
@@ -227,8 +252,11 @@ class KITTIPairs(object):
             sat = im.convert("RGB")
         with open(oxts_path) as f:
             heading = float(f.readline().split(" ")[5])
-        with Image.open(grd_path, "r") as im:
-            grd = np.array(im.convert("RGB"))
+        if cached is not None and "grd" in cached:
+            grd = None
+        else:
+            with Image.open(grd_path, "r") as im:
+                grd = np.array(im.convert("RGB"))
         sx, sy, ori = self.perturbation(idx) if draws is None else draws
         mpp = self.meter_per_pixel
         w, h = sat.size
@@ -280,7 +308,7 @@ class OxfordPairs(object):
         from PIL import Image
         if split not in OXFORD_LISTS:
             raise ValueError("split must be 'train', 'val' or 'test'")
-        self.root, self.split = grd_image_root, split
+        self.root, self.split, self.sat_path = grd_image_root, split, sat_path
         Image.MAX_IMAGE_PIXELS = None                                  # the real map is 16 k x 19 k pixels
         self.map = Image.open(sat_path)
         self.map.load()
@@ -317,12 +345,37 @@ class OxfordPairs(object):
         """The sample's random choice (see VIGORPairs.draw): the patch offset in training, nothing otherwise."""
         return self.offset() if self.split == "train" else None
 
-    def sample(self, idx, sat_hw=(512, 512), grd_hw=(154, 231), draws=None):
+    def _position(self, idx):
+        """(column, row) of the vehicle on the map — one sample at a time, as the reference evaluates it (a batched product may
+        round differently in the last place)."""
+        return tuple(float(v) for v in np.dot(np.hstack([self.utm[idx:idx + 1], np.ones((1, 1))]), self.affine)[0, :2])
+
+    @staticmethod
+    def _grid(v):
+        """(k, p): patch origin 400 * k such that the vehicle sits at p in [200, 600) of the patch (val / test)."""
+        k = int(v // 400)
+        if np.round(v - 400 * k) < 200:
+            k -= 1
+        return k, int(np.round(v - 400 * k))
+
+    def keys(self, idx, draws):
+        """Sources of sample idx for a device image cache: the camera image's path and — val / test — "<map path>@<kc>,<kr>",
+        the grid patch; a training patch has a random offset: None."""
+        sat = None
+        if self.split != "train":
+            col, row = self._position(idx)
+            sat = "%s@%d,%d" % (self.sat_path, self._grid(col)[0], self._grid(row)[0])
+        return {"grd": os.path.join(self.root, self.rows[idx][0]), "sat": sat}
+
+    def sample(self, idx, sat_hw=(512, 512), grd_hw=(154, 231), draws=None, cached=None):
+        """cached: {side: raw (h, w)} of the sides a device image cache holds: not opened / cropped, their *_u8 entry is None."""
         from PIL import Image
-        with Image.open(os.path.join(self.root, self.rows[idx][0])) as im:
-            grd = np.array(im.convert("RGB"))
-        # one sample at a time, as the reference evaluates it (a batched product may round differently in the last place)
-        col, row = (float(v) for v in np.dot(np.hstack([self.utm[idx:idx + 1], np.ones((1, 1))]), self.affine)[0, :2])
+        if cached is not None and "grd" in cached:
+            grd = None
+        else:
+            with Image.open(os.path.join(self.root, self.rows[idx][0])) as im:
+                grd = np.array(im.convert("RGB"))
+        col, row = self._position(idx)
         if self.split == "train":
             drow, dcol = self.offset() if draws is None else draws
             r0, c0 = int(row + drow), int(col + dcol)
@@ -330,17 +383,12 @@ class OxfordPairs(object):
             cy = int(np.round((400 + drow) / 800 * 512 - 256))
             cx = int(np.round((400 + dcol) / 800 * 512 - 256))
         else:
-            def grid(v):                    # patch origin = a multiple of 400 such that the vehicle sits in [200, 600) of the patch
-                k = int(v // 400)
-                if np.round(v - 400 * k) < 200:
-                    k -= 1
-                return k, int(np.round(v - 400 * k))
-            kc, pc = grid(col)
-            kr, pr = grid(row)
+            kc, pc = self._grid(col)
+            kr, pr = self._grid(row)
             box = (kc * 400, kr * 400, kc * 400 + 800, kr * 400 + 800)
             cy = int(-(pr / 800 * 512 - 256))
             cx = int(-(pc / 800 * 512 - 256))
-        sat = np.array(self.map.crop(box).convert("RGB"))
+        sat = None if cached is not None and "sat" in cached else np.array(self.map.crop(box).convert("RGB"))
         angle = float(self.yaw[idx]) / np.pi * 180 - 90                          # 0 = north, clockwise (datasets.py:334-337)
         if angle < 0:
             angle += 360
@@ -398,12 +446,20 @@ class DeviceBatches(object):
     the same on every rank BY CONSTRUCTION — required for training, where each step all-reduces gradients inside the
     backward and a rank with one batch more would wait for its peers until the RCCL timeout.  Default: "pad" for a TRAINING
     split (`pairs_is_training`; an index object that does not say: when targets are produced) and world > 1, else "exact" —
-    a test split is never padded by default, with or without targets."""
+    a test split is never padded by default, with or without targets.
+
+    cache (ccvpe_amd.cache.DeviceImageCache, opt-in): the resized uint8 image of every source file stays on the device.  The
+    producer thread asks the index for the sample's `keys`, looks them up and decodes only what is missing; the consumer
+    inserts the misses (a key once per batch) and assembles each side of the batch with ONE ccvpe_gather_norm_u8_f32 launch
+    over a table of slot addresses.  Sides without a key (KITTI's aligned crop, Oxford's training patch), blank panoramas and
+    the misses of a full cache go through the cache's scratch slots and the same launch.  Draws are made in the same order and
+    the batches are bit-identical to those without a cache."""
 
     def __init__(self, pairs, batch_size, device="cuda", indices=None, shuffle=False, seed=0, rank=0, world=1, workers=8,
                  prefetch=2, grd_hw=(320, 640), sat_hw=(512, 512), fov=360, targets=True, n_bins=20, drop_last=False,
-                 ascending_bins=False, shard=None):
+                 ascending_bins=False, shard=None, cache=None):
         self.pairs, self.batch_size, self.device = pairs, int(batch_size), torch.device(device)
+        self.cache = cache                                   # ccvpe_amd.cache.DeviceImageCache, or None: the path without one
         idx = np.arange(len(pairs)) if indices is None else np.asarray(indices)
         if shuffle:
             idx = idx[np.random.default_rng(seed).permutation(len(idx))]      # same permutation on every rank
@@ -427,7 +483,70 @@ class DeviceBatches(object):
     def _decode_batch(self, pool, chunk):
         # the random choices of the chunk are drawn HERE, on the producer thread, in index order; the pool only decodes
         draws = [self.pairs.draw(int(i)) for i in chunk]
+        if self.cache is not None:
+            return self._decode_batch_cached(pool, chunk, draws)
         return list(pool.map(lambda a: self.pairs.sample(int(a[0]), self.sat_hw, self.grd_hw, draws=a[1]), zip(chunk, draws)))
+
+    def _cache_key(self, side, key):
+        """The cache holds RESIZED images: the key carries the side's size, so iterators of different geometry can share one."""
+        hw = self.grd_hw if side == "grd" else self.sat_hw
+        return "%s|%dx%d" % (key, hw[0], hw[1])
+
+    def _decode_batch_cached(self, pool, chunk, draws):
+        """Producer thread, with a cache: keys -> lookup -> decode only the sides that are missing.  Each sample carries its
+        cache keys (`_keys`) and the slot addresses found (`_addr`) to the consumer."""
+        keys, found = [], []
+        for i, d in zip(chunk, draws):
+            k = self.pairs.keys(int(i), d)
+            k = {side: None if k[side] is None else self._cache_key(side, k[side]) for side in ("grd", "sat")}
+            keys.append(k)
+            hits = {side: self.cache.lookup(k[side]) for side in ("grd", "sat") if k[side] is not None}
+            found.append({side: hit for side, hit in hits.items() if hit is not None})
+
+        def one(a):
+            i, d, k, f = a
+            s = self.pairs.sample(int(i), self.sat_hw, self.grd_hw, draws=d, cached={side: hit[1] for side, hit in f.items()})
+            s["_keys"], s["_addr"] = k, {side: hit[0] for side, hit in f.items()}
+            return s
+
+        return list(pool.map(one, zip(chunk, draws, keys, found)))
+
+    def _gather_side(self, samples, side, hw, keep_w, dst, crops=None):
+        """One side of a batch through the cache: insert the misses (a key once), resize what cannot be retained into scratch
+        slots, then ONE gather launch over the address table."""
+        from . import preprocess
+        cache, dev = self.cache, self.device
+        scratch, used = None, 0
+        addrs, done = [], {}
+        for i, s in enumerate(samples):
+            key = s["_keys"][side]
+            if side in s.get("nocache", ()):
+                key = None
+            addr = s["_addr"].get(side)
+            if addr is None and key is not None:             # inserted by an earlier sample of this batch, or by a batch that
+                addr = done.get(key) or cache.address(key)   # was still in flight when the producer looked the key up
+            if addr is None:
+                if crops is not None:
+                    img = crops[i]
+                    if tuple(img.shape[:2]) == tuple(hw):    # the align kernel's crop already has the model's size: no resize
+                        addr = img.data_ptr()
+                else:
+                    img = torch.from_numpy(s[side + "_u8"]).to(dev, non_blocking=True)
+                if addr is None and key is not None:
+                    addr = cache.insert(key, img, hw)
+                    if addr is not None:
+                        done[key] = addr
+                if addr is None:
+                    if scratch is None:
+                        scratch = cache.scratch(len(samples), hw)
+                    slot = scratch[used]
+                    used += 1
+                    preprocess.resize_u8(img, hw, dst=slot)
+                    addr = slot.data_ptr()
+            addrs.append(addr)
+        table = torch.tensor(addrs, dtype=torch.int64, device=dev)
+        rolls = torch.tensor([int(s["roll"]) if side == "grd" else 0 for s in samples], dtype=torch.int32, device=dev)
+        preprocess.gather_norm(table, rolls, hw, keep_w=keep_w, dst=dst)
 
     def _align_on_device(self, samples):
         """KITTIPairs(device_align=True): the batch's decoded maps packed into ONE pinned staging buffer (reused across batches),
@@ -457,11 +576,15 @@ class DeviceBatches(object):
         out.grd = torch.empty((b, 3, self.grd_hw[0], self.keep_w), device=dev, dtype=torch.float32)
         out.sat = torch.empty((b, 3) + self.sat_hw, device=dev, dtype=torch.float32)
         crops = self._align_on_device(samples) if b and "align" in samples[0] else None
-        for i, s in enumerate(samples):
-            g = torch.from_numpy(s["grd_u8"]).to(dev, non_blocking=True)
-            a = torch.from_numpy(s["sat_u8"]).to(dev, non_blocking=True) if crops is None else crops[i]
-            preprocess.preprocess(g, self.grd_hw, dst=out.grd[i], roll=s["roll"], keep_w=self.keep_w)
-            preprocess.preprocess(a, self.sat_hw, dst=out.sat[i])
+        if self.cache is not None:
+            self._gather_side(samples, "grd", self.grd_hw, self.keep_w, out.grd)
+            self._gather_side(samples, "sat", self.sat_hw, self.sat_hw[1], out.sat, crops=crops)
+        else:
+            for i, s in enumerate(samples):
+                g = torch.from_numpy(s["grd_u8"]).to(dev, non_blocking=True)
+                a = torch.from_numpy(s["sat_u8"]).to(dev, non_blocking=True) if crops is None else crops[i]
+                preprocess.preprocess(g, self.grd_hw, dst=out.grd[i], roll=s["roll"], keep_w=self.keep_w)
+                preprocess.preprocess(a, self.sat_hw, dst=out.sat[i])
         out.angle_deg = torch.tensor([s["angle_deg"] for s in samples], device=dev, dtype=torch.float32)
         out.heading_deg = torch.tensor([s["angle_deg"] for s in samples], device=dev, dtype=torch.float64)
         out.center = torch.tensor([s["center"] for s in samples], device=dev, dtype=torch.float32)

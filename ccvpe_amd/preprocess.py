@@ -101,3 +101,50 @@ def preprocess_batch(images_u8, out_hw, rolls=None, keep_w=None, mean=IMAGENET_M
     for i, img in enumerate(images_u8):
         preprocess(img, out_hw, dst=out[i], roll=0 if rolls is None else int(rolls[i]), keep_w=keep, mean=mean, std=std)
     return out
+
+
+def resize_u8(img_u8, out_hw, dst=None):
+    """img_u8: decoded image [H,W,3] uint8 on the device.  Writes / returns dst [h, w, 3] uint8 (e.g. a slot of the device
+    image cache): PIL.Image.resize((w, h), BILINEAR) bit for bit — the per-file half of `preprocess`, kept as bytes."""
+    lib = _lib.load()
+    if not (img_u8.is_cuda and img_u8.dtype == torch.uint8 and img_u8.is_contiguous() and img_u8.dim() == 3
+            and img_u8.shape[2] == 3):
+        raise ValueError("img_u8 must be a contiguous [H,W,3] uint8 device tensor (no CPU fallback)")
+    h_in, w_in = int(img_u8.shape[0]), int(img_u8.shape[1])
+    h, w = out_hw
+    if dst is None:
+        dst = torch.empty((h, w, 3), device=img_u8.device, dtype=torch.uint8)
+    ops._chk(dst, "dst", torch.uint8)
+    if dst.numel() != h * w * 3:
+        raise ValueError("dst must hold [%d,%d,3] bytes" % (h, w))
+    xb, xc, xk = _tables_on(img_u8.device, w_in, w)
+    yb, yc, yk = _tables_on(img_u8.device, h_in, h)
+    tmp = torch.empty((h_in, w, 3), device=img_u8.device, dtype=torch.uint8)
+    check(lib.ccvpe_resize_u8(img_u8.data_ptr(), h_in, w_in, xb.data_ptr(), xc.data_ptr(), xk, yb.data_ptr(), yc.data_ptr(), yk,
+                              tmp.data_ptr(), dst.data_ptr(), h, w, ops._stream()), "ccvpe_resize_u8")
+    return dst
+
+
+def gather_norm(addresses, rolls, hw, keep_w=None, dst=None, mean=IMAGENET_MEAN, std=IMAGENET_STD):
+    """ONE launch for a batch side: addresses int64 [B] (device) = device addresses of resized [h, w, 3] uint8 images (slots
+    of the device image cache, or any live uint8 device memory of that size), rolls int32 [B] (device).  Writes / returns
+    dst [B, 3, h, keep_w] fp32: ToTensor -> Normalize -> torch.roll(shifts=rolls[b], dims=W) -> [..., :keep_w], bit-identical
+    to `preprocess` on the image the slot was resized from.  The caller keeps the addressed memory alive."""
+    lib = _lib.load()
+    ops._chk(addresses, "addresses", torch.int64)
+    ops._chk(rolls, "rolls", torch.int32)
+    b = int(addresses.shape[0])
+    if addresses.dim() != 1 or tuple(rolls.shape) != (b,):
+        raise ValueError("addresses and rolls must both be [B]")
+    h, w = hw
+    keep = w if keep_w is None else int(keep_w)
+    if dst is None:
+        dst = torch.empty((b, 3, h, keep), device=addresses.device, dtype=torch.float32)
+    ops._chk(dst, "dst")
+    if tuple(dst.shape) != (b, 3, h, keep):
+        raise ValueError("dst must be [%d,3,%d,%d]" % (b, h, keep))
+    m = (ctypes.c_float * 3)(*mean)
+    s = (ctypes.c_float * 3)(*std)
+    check(lib.ccvpe_gather_norm_u8_f32(addresses.data_ptr(), rolls.data_ptr(), b, h, w, keep, m, s, dst.data_ptr(),
+                                       ops._stream()), "ccvpe_gather_norm_u8_f32")
+    return dst

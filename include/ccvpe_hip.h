@@ -671,6 +671,24 @@ int ccvpe_preprocess_u8_f32(const unsigned char* src, int in_h, int in_w, const 
                             void* stream);
 
 /* -------------------------------------------------------------------------------------------
+ * Device-resident image cache (csrc/preprocess.hip; ccvpe_amd/cache.py): the per-file half of the input pipeline
+ * (the Pillow-exact resize) kept as uint8 in HBM, and the per-epoch half (roll, FoV crop, ToTensor, Normalize) as ONE
+ * launch per batch and side.
+ *   resize_u8: the horizontal pass of the entry point above, then a vertical pass that writes the clipped bytes:
+ *   dst_u8 [out_h][out_w][3] uint8 = PIL.Image.resize((out_w, out_h), BILINEAR) bit for bit.  Tables and tmp as above.
+ *   gather_norm: srcs [batch] int64 (device) = DEVICE ADDRESSES of resized [h][w][3] uint8 images (a pointer table: the
+ *   images may lie in any number of allocations), rolls [batch] int32 (device) = torch.roll shifts, any sign and size;
+ *   dst [batch][3][h][keep_w] fp32, dst[b][c][y][x] = ((float)src_b[y][(x - roll_b) mod w][c] / 255 - mean[c]) / std[c]
+ *   with the arithmetic of the entry point above (bit-identical to it).  mean / std: HOST pointers to 3 floats.
+ *   keep_w <= w; batch == 0 succeeds without a launch; batch <= 65535.
+ * ----------------------------------------------------------------------------------------- */
+int ccvpe_resize_u8(const unsigned char* src, int in_h, int in_w, const int* xbounds, const int* xcoef, int xksize,
+                    const int* ybounds, const int* ycoef, int yksize, unsigned char* tmp, unsigned char* dst_u8,
+                    int out_h, int out_w, void* stream);
+int ccvpe_gather_norm_u8_f32(const long long* srcs, const int* rolls, int batch, int h, int w, int keep_w,
+                             const float* mean, const float* stdv, float* dst, void* stream);
+
+/* -------------------------------------------------------------------------------------------
  * KITTI aerial alignment (csrc/align.hip; the reference's datasets.py:443-464 / :577-596): PIL's rotate (NEAREST, 16.16
  * fixed point) -> two BILINEAR translations (float64, truncated) -> rotate -> centre crop, evaluated lazily per pixel
  * of the crop, bit-identical to Pillow.  ONE launch per batch.
