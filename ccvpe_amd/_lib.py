@@ -83,6 +83,7 @@ PROTOTYPES = {
     "ccvpe_mbconv_band_plan": (c_int, [c_int] * 7),
     "ccvpe_conv3x3_variant": (c_int, [ctypes.POINTER(ConvDesc), c_int]),
     "ccvpe_set_match_mfma": (c_int, [c_int]),
+    "ccvpe_match_route": (c_int, [c_int, c_int, ctypes.POINTER(c_int)] + [c_int] * 10 + [ctypes.POINTER(c_int)]),
     "ccvpe_set_pwn_kernels": (c_int, [c_int]),
     "ccvpe_conv3x3_wino_ok": (c_int, [ctypes.POINTER(ConvDesc)]),
     "ccvpe_conv3x3_wino_f32": (c_int, [ctypes.POINTER(ConvDesc), c_void_p]),

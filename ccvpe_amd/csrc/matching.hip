@@ -550,42 +550,34 @@ __global__ __launch_bounds__(256) void match_stream_kernel(const MatchStreamPara
 
 using namespace ccvpe;
 
-template <typename TX, int NPAD, bool PARTIAL, int VEC, bool MFMA = false>
-static int launch_match(const TX* x, int ldx, const float* g, int ldg, int L, const MatchOffsets& mo, int n_shifts,
-                        int n_max, int n_tail, float* scores, TX* dstx, int ldo, int B, int hw, int C,
-                        hipStream_t st) {
-  const int lpp = match_lpp(C);
-  int lpp_log2 = 0;
-  while ((1 << lpp_log2) < lpp) ++lpp_log2;
-  const int S = MFMA ? match_pitch_mfma(C) : match_pitch(C, lpp);
-  const int tp = 256 / lpp;
-  const int tl = MFMA ? 2 * C + 16 : 2 * C;
-  const int pbuf = (MFMA && tp < 64) ? 4 * ((PARTIAL ? 2 : 1) * NPAD + 1) * 16 : 0;
-  const size_t smem = sizeof(float) * ((size_t)tl * (PARTIAL ? 2 : 1) + (size_t)tp * S + (size_t)n_shifts * tp + 2 * tp + 4 + pbuf);
-  if (smem > 160 * 1024) return fail(CCVPE_EINVAL, "match_level: C=%d needs %zu B of LDS", C, smem);
-  auto kern = match_kernel<TX, NPAD, PARTIAL, VEC, MFMA>;
-  static DevCache lds_set;                         // per instantiation: the largest size asked for so far
-  if (int rc = ensure_dyn_lds(lds_set, kern, (int)smem, "match_level")) return rc;
-  if (B > 65535) return fail(CCVPE_EINVAL, "match_level: batch > 65535");
-  dim3 grid((hw + tp - 1) / tp, B);
-  hipLaunchKernelGGL(kern, grid, dim3(256), smem, st, x, ldx, g, ldg, L, mo, n_shifts, n_max, n_tail, scores, dstx,
-                     ldo, hw, C, lpp_log2, S);
-  return check_launch("match_kernel");
-}
-
 static int g_match_mfma = 2;   // 0 vector-ALU form everywhere, 1 + the tiled matrix-core form, 2 + the streaming form of the narrow levels
 
-template <typename TX>
-static int match_any(const TX* x, int ldx, const float* g, int ldg, int L, const int* shifts, int n_shifts, int n_max,
-                     int n_tail, int stride, int window_offset, float* scores, TX* dstx, int ldo, int B, int hw, int C,
-                     void* stream) {
+// The one decision: which kernel form serves a matching call, which instantiation of it, and the tile geometry the launch uses.
+// Host arithmetic only (no device call), so ccvpe_match_route can answer it on a machine without a GPU; the streaming form's
+// tiles per wave depend on the CU count and are worked out at the launch.
+enum { MATCH_VALU = 0, MATCH_TILED = 1, MATCH_STREAM = 2 };
+struct MatchRoute {
+  int form;                // MATCH_*
+  int npad;                // hypothesis rows of the instantiation (16 MTL for the streaming form)
+  int partial, vec;        // vec: 0 for the streaming form (it builds its fragments element by element)
+  int nb;                  // streaming form: 16-channel blocks held in registers
+  int lpp, tp, npt, ks;    // tiled forms: lanes per pixel, pixels per workgroup; matrix-core form: 16-pixel tiles, K slices
+  int S;                   // tiled forms: LDS row pitch (floats)
+  size_t lds;              // tiled forms: dynamic LDS bytes
+  MatchOffsets mo;
+};
+
+// ldg / ptrs_aligned: what the launch knows and the query does not (the query passes ldg = L, true)
+static int match_route(int elem_size, int ldx, int ldg, int L, const int* shifts, int n_shifts, int n_max, int n_tail, int stride,
+                       int window_offset, int ldo, int B, int hw, int C, bool ptrs_aligned, MatchRoute& r) {
+  if (elem_size != 4 && elem_size != 2) return fail(CCVPE_EINVAL, "match_level: element size %d (4 = fp32, 2 = bf16)", elem_size);
   if (n_shifts < 1 || n_shifts > CCVPE_MAX_SHIFTS) return fail(CCVPE_EINVAL, "match_level: n_shifts %d out of range", n_shifts);
   if (n_max < 1 || n_max > n_shifts || n_tail < 0 || n_tail > n_shifts) return fail(CCVPE_EINVAL, "match_level: bad n_max/n_tail");
   if (C % 8 || ldx % 4 || ldo % 4 || ldo < C + 1 + n_tail) return fail(CCVPE_EINVAL, "match_level: C%%8, ldx%%4, ldo%%4, ldo>=C+1+n_tail required");
-  if (sizeof(TX) == 2 && ldx % 8) return fail(CCVPE_EINVAL, "match_level: bf16 rows must be 16-byte aligned (ldx %% 8)");
+  if (elem_size == 2 && ldx % 8) return fail(CCVPE_EINVAL, "match_level: bf16 rows must be 16-byte aligned (ldx %% 8)");
   if (L < 1 || L > C || L > ldg) return fail(CCVPE_EINVAL, "match_level: bad L");
-  if (!aligned16(x) || !aligned16(dstx)) return fail(CCVPE_EINVAL, "match_level: x/dstx must be 16-byte aligned");
-  MatchOffsets mo;
+  if (!ptrs_aligned) return fail(CCVPE_EINVAL, "match_level: x/dstx must be 16-byte aligned");
+  MatchOffsets& mo = r.mo;
   for (int i = 0; i < CCVPE_MAX_SHIFTS; ++i) {
     long o = 0;
     if (i < n_shifts) {
@@ -600,11 +592,66 @@ static int match_any(const TX* x, int ldx, const float* g, int ldg, int L, const
     if (mo.off[i] % 4 && vec > 2) vec = 2;
     if (mo.off[i] % 2) vec = 1;
   }
-  hipStream_t st = (hipStream_t)stream;
-#define M_ARGS x, ldx, g, ldg, L, mo, n_shifts, n_max, n_tail, scores, dstx, ldo, B, hw, C, st
+  r.partial = partial;
+  r.vec = r.nb = r.lpp = r.tp = r.npt = r.ks = r.S = 0;
+  r.lds = 0;
   // narrow levels with many hypotheses: every wave streams its own run of 16-pixel tiles (no LDS tile, no barriers)
   if (g_match_mfma >= 2 && n_shifts >= 9 && n_shifts <= 32 && n_tail == 0 && C <= 80 && hw % 16 == 0 && (long)B * hw >= 65536 &&
-      ldo - C <= 64 && (sizeof(TX) == 4 || ldo % 4 == 0)) {
+      ldo - C <= 64) {
+    const int nb = (C + 15) / 16;
+    r.form = MATCH_STREAM;
+    r.npad = n_shifts <= 16 ? 16 : 32;
+    r.nb = nb <= 2 ? 2 : (nb >= 5 ? 5 : nb);
+    return CCVPE_OK;
+  }
+  const bool mfma = g_match_mfma && n_shifts >= 9 && n_shifts <= 32 && vec >= 2;   // many hypotheses: the circulant product on the matrix cores
+  r.form = mfma ? MATCH_TILED : MATCH_VALU;
+  r.npad = mfma ? (n_shifts <= 16 ? 16 : 32) : (n_shifts <= 1 ? 1 : n_shifts <= 8 ? 8 : n_shifts <= 16 ? 16 : n_shifts <= 24 ? 24 : 48);
+  r.vec = vec;
+  r.lpp = match_lpp(C);
+  r.tp = 256 / r.lpp;
+  r.S = mfma ? match_pitch_mfma(C) : match_pitch(C, r.lpp);
+  if (mfma) {
+    r.npt = r.tp >= 16 ? r.tp >> 4 : 1;
+    r.ks = r.npt >= 4 ? 1 : 4 / r.npt;
+  }
+  const int tl = mfma ? 2 * C + 16 : 2 * C;
+  const int pbuf = (mfma && r.ks > 1) ? 4 * ((partial ? 2 : 1) * r.npad + 1) * 16 : 0;
+  r.lds = sizeof(float) * ((size_t)tl * (partial ? 2 : 1) + (size_t)r.tp * r.S + (size_t)n_shifts * r.tp + 2 * r.tp + 4 + pbuf);
+  if (r.lds > 160 * 1024) return fail(CCVPE_EINVAL, "match_level: C=%d needs %zu B of LDS", C, r.lds);
+  if (B > 65535) return fail(CCVPE_EINVAL, "match_level: batch > 65535");
+  return CCVPE_OK;
+}
+
+template <typename TX, int NPAD, bool PARTIAL, int VEC, bool MFMA = false>
+static int launch_match(const MatchRoute& r, const TX* x, int ldx, const float* g, int ldg, int L, int n_shifts,
+                        int n_max, int n_tail, float* scores, TX* dstx, int ldo, int B, int hw, int C,
+                        hipStream_t st) {
+  int lpp_log2 = 0;
+  while ((1 << lpp_log2) < r.lpp) ++lpp_log2;
+  auto kern = match_kernel<TX, NPAD, PARTIAL, VEC, MFMA>;
+  static DevCache lds_set;                         // per instantiation: the largest size asked for so far
+  if (int rc = ensure_dyn_lds(lds_set, kern, (int)r.lds, "match_level")) return rc;
+  dim3 grid((hw + r.tp - 1) / r.tp, B);
+  hipLaunchKernelGGL(kern, grid, dim3(256), r.lds, st, x, ldx, g, ldg, L, r.mo, n_shifts, n_max, n_tail, scores, dstx,
+                     ldo, hw, C, lpp_log2, r.S);
+  return check_launch("match_kernel");
+}
+
+template <typename TX>
+static int match_any(const TX* x, int ldx, const float* g, int ldg, int L, const int* shifts, int n_shifts, int n_max,
+                     int n_tail, int stride, int window_offset, float* scores, TX* dstx, int ldo, int B, int hw, int C,
+                     void* stream) {
+  MatchRoute r;
+  if (int rc = match_route((int)sizeof(TX), ldx, ldg, L, shifts, n_shifts, n_max, n_tail, stride, window_offset, ldo, B, hw, C,
+                           aligned16(x) && aligned16(dstx), r))
+    return rc;
+  const MatchOffsets& mo = r.mo;
+  const bool partial = r.partial;
+  const int vec = r.vec;
+  hipStream_t st = (hipStream_t)stream;
+#define M_ARGS r, x, ldx, g, ldg, L, n_shifts, n_max, n_tail, scores, dstx, ldo, B, hw, C, st
+  if (r.form == MATCH_STREAM) {
     MatchStreamParams q;
     q.x = x; q.g = g; q.scores = scores; q.dstx = dstx; q.mo = mo;
     q.ldx = ldx; q.ldg = ldg; q.L = L; q.n_shifts = n_shifts; q.n_max = n_max; q.ldo = ldo; q.hw = hw; q.C = C;
@@ -612,17 +659,17 @@ static int match_any(const TX* x, int ldx, const float* g, int ldg, int L, const
     const int waves = 2 * num_cus() * 4;
     q.tpw = (q.tiles + waves - 1) / waves;
     const int wgs = ((q.tiles + q.tpw - 1) / q.tpw + 3) / 4;
-    const int nb = (C + 15) / 16;
+    const int nb = r.nb;
 #define MS_GO(MTL_, P_, NB_) hipLaunchKernelGGL((match_stream_kernel<TX, MTL_, P_, NB_>), dim3(wgs), dim3(256), 0, st, q)
 #define MS_NB(MTL_, P_) \
     if (nb <= 2) MS_GO(MTL_, P_, 2); else if (nb == 3) MS_GO(MTL_, P_, 3); else if (nb == 4) MS_GO(MTL_, P_, 4); else MS_GO(MTL_, P_, 5)
-    if (n_shifts <= 16) { if (partial) { MS_NB(1, true); } else { MS_NB(1, false); } }
+    if (r.npad == 16) { if (partial) { MS_NB(1, true); } else { MS_NB(1, false); } }
     else { if (partial) { MS_NB(2, true); } else { MS_NB(2, false); } }
 #undef MS_NB
 #undef MS_GO
     return check_launch("match_stream_kernel");
   }
-  if (g_match_mfma && n_shifts >= 9 && n_shifts <= 32 && vec >= 2) {       // many hypotheses: the circulant product on the matrix cores
+  if (r.form == MATCH_TILED) {
 #define M_MFMA(NP)                                                          \
     if (partial) {                                                          \
       if (vec == 4) return launch_match<TX, NP, true, 4, true>(M_ARGS);     \
@@ -630,12 +677,12 @@ static int match_any(const TX* x, int ldx, const float* g, int ldg, int L, const
     }                                                                       \
     if (vec == 4) return launch_match<TX, NP, false, 4, true>(M_ARGS);      \
     return launch_match<TX, NP, false, 2, true>(M_ARGS);
-    if (n_shifts <= 16) { M_MFMA(16) }
+    if (r.npad == 16) { M_MFMA(16) }
     M_MFMA(32)
 #undef M_MFMA
   }
 #define M_DISPATCH(NP)                                              \
-  if (n_shifts <= NP) {                                             \
+  if (r.npad == NP) {                                               \
     if (partial) {                                                  \
       if (vec == 4) return launch_match<TX, NP, true, 4>(M_ARGS);   \
       if (vec == 2) return launch_match<TX, NP, true, 2>(M_ARGS);   \
@@ -655,6 +702,19 @@ extern "C" int ccvpe_set_match_mfma(int on) {
   const int old = g_match_mfma;
   g_match_mfma = on < 0 ? 0 : (on > 2 ? 2 : on);
   return old;
+}
+
+extern "C" int ccvpe_match_route(int elem_size, int L, const int* shifts, int n_shifts, int n_max, int n_tail, int stride,
+                                 int window_offset, int ldx, int ldo, int B, int hw, int C, int* out) {
+  if (!shifts) return fail(CCVPE_EINVAL, "match_route: null shifts");
+  MatchRoute r;
+  if (int rc = match_route(elem_size, ldx, L, L, shifts, n_shifts, n_max, n_tail, stride, window_offset, ldo, B, hw, C, true, r))
+    return rc;
+  if (out) {
+    const int v[CCVPE_MATCH_ROUTE_INTS] = {r.npad, r.partial, r.vec, r.nb, r.lpp, r.tp, r.npt, r.ks, r.S, (int)r.lds};
+    for (int i = 0; i < CCVPE_MATCH_ROUTE_INTS; ++i) out[i] = v[i];
+  }
+  return r.form;
 }
 
 extern "C" int ccvpe_match_level_f32(const float* x, int ldx, const float* g, int ldg, int L, const int* shifts,

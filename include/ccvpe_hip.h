@@ -348,6 +348,18 @@ int ccvpe_ground_descriptor_f32(const float* y1, int ld, const float* wh, const 
  * form for every configuration, 1 = the tiled matrix-core form, 2 (default) = additionally the streaming form of the narrow levels
  * (C <= 80, no tail scores, >= 65 536 pixels: every wave streams 16-pixel tiles, no LDS).  Returns the previous setting. */
 int ccvpe_set_match_mfma(int on);
+/* Which kernel form ccvpe_match_level_f32 (elem_size 4) / _bf16 (elem_size 2) launches for these arguments, decided by the same
+ * host function as the launch and without touching the device: returns 0 = vector-ALU form, 1 = tiled matrix-core form,
+ * 2 = streaming form (it honours ccvpe_set_match_mfma), or the negative error code the launch would return (the pointer
+ * alignment and ldg checks excepted: the query takes neither).  out (may be NULL) receives CCVPE_MATCH_ROUTE_INTS ints, 0 where a
+ * field does not apply to the form: [0] NPAD, the hypothesis rows of the instantiation (16 MTL for the streaming form),
+ * [1] PARTIAL (L < channels), [2] VEC, the widest aligned read of the descriptor table (tiled forms), [3] NB, the 16-channel
+ * blocks of the streaming form, [4] LPP lanes per pixel and [5] TP pixels per workgroup (tiled forms), [6] NPT 16-pixel tiles
+ * and [7] KS K slices per tile (matrix-core form), [8] the LDS row pitch S in floats and [9] the dynamic LDS bytes (tiled
+ * forms).  The streaming form's tiles per wave depend on the device's CU count and are not reported. */
+#define CCVPE_MATCH_ROUTE_INTS 10
+int ccvpe_match_route(int elem_size, int L, const int* shifts, int n_shifts, int n_max, int n_tail, int stride,
+                      int window_offset, int ldx, int ldo, int batch, int hw, int channels, int* out);
 /* -------------------------------------------------------------------------------------------
  * Rotational matching + LMU concat, fused (models.py:186-205 and the five blocks after it;
  * ori_prior :484-514; KITTI :788-806):
