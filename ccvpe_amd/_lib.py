@@ -97,6 +97,7 @@ PROTOTYPES = {
     "ccvpe_upconv3x3_s3_ok": (c_int, [ctypes.POINTER(UpconvDesc)]),
     "ccvpe_upconv3x3_s3_f32": (c_int, [ctypes.POINTER(UpconvDesc), c_void_p]),
     "ccvpe_upconv3x3_s3_form_ok": (c_int, [ctypes.POINTER(UpconvDesc), c_int]),
+    "ccvpe_upconv3x3_s3_route": (c_int, [ctypes.POINTER(UpconvDesc), c_int]),
     "ccvpe_upconv3x3_s3_form_f32": (c_int, [ctypes.POINTER(UpconvDesc), c_int, c_void_p]),
     "ccvpe_set_s3_quad": (c_int, [c_int]),
     "ccvpe_stem_conv_f32": (c_int, [c_void_p] * 5 + [c_int] * 4 + [c_void_p]),

@@ -288,11 +288,20 @@ int c3n_match_dispatch(const IgemmParams& p, int batch, const float* g, int ldg,
 extern bool g_use_pwn;                                    // ccvpe_set_pwn_kernels
 bool pwn_supported(const IgemmParams& p, int batch, int esz);
 int pwn_dispatch(const IgemmParams& p, int batch, int esz, hipStream_t stream);
-int up2_supported(int c0, int c1, int n, int kpad, int h1, int w1, int batch);
-int up2_dispatch(const void* src0, const void* src1, const void* w, const float* shift9, void* dst, int c0, int ld0, int c1, int ld1,
-                 int h1, int w1, int n, int kpad, int ldd, int act, int batch, hipStream_t stream);
-// upconv_s3q.hip: the four-parities-per-workgroup form of upconv_s3.hip's layer, for a desc that file's checks have accepted
+int up2_supported(int c0, int c1, int n, int kpad, int h1, int w1, int batch);      // 0 = not served, else an instantiation id
+int up2_launch(int id, const ccvpe_upconv_desc* d, hipStream_t stream);
+// upconv_s3q.hip: the four-parities-per-workgroup form of upconv_s3.hip's layer, for a desc that file's s3_pick() has accepted
 bool upconv_s3q_serves(const ccvpe_upconv_desc* d);
-int upconv_s3q_launch(const ccvpe_upconv_desc* d, hipStream_t stream);
+int upconv_s3q_launch(const ccvpe_upconv_desc* d, hipStream_t stream);      // (a desc s3_pick() routed to the quad form)
+
+// descriptor -> the fields UpS3Params (upconv_s3.hip) and UpS3qParams (upconv_s3q.hip) share
+template <typename P>
+static void s3_fill(const ccvpe_upconv_desc* d, P& p) {
+  p.src0 = reinterpret_cast<const float*>(d->src0); p.src1 = reinterpret_cast<const float*>(d->src1);
+  p.w = d->w; p.shift9 = d->shift9; p.dst = reinterpret_cast<float*>(d->dst);
+  p.c0 = d->c0; p.ld0 = d->ld0; p.c1 = d->c1; p.ld1 = d->ld1;
+  p.H1 = d->h1; p.W1 = d->w1; p.batch = d->batch; p.N = d->n; p.ldd = d->ldd; p.act = d->act;
+  p.nb0 = (d->c0 + 15) / 16; p.nb1 = (d->c1 + 15) / 16; p.nst = 4 * p.nb0 + 9 * p.nb1;
+}      // (the grid: the launch)
 
 }  // namespace ccvpe

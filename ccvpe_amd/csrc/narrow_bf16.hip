@@ -87,19 +87,16 @@ int up2_supported(int c0, int c1, int n, int kpad, int h1, int w1, int batch) {
   return id;
 }
 
-int up2_dispatch(const void* src0, const void* src1, const void* w, const float* shift9, void* dst, int c0, int ld0, int c1, int ld1,
-                 int h1, int w1, int n, int kpad, int ldd, int act, int batch, hipStream_t stream) {
-  const int id = up2_supported(c0, c1, n, kpad, h1, w1, batch);
-  if (!id) return fail(CCVPE_EINVAL, "up2: unsupported layer");
-  if (act != CCVPE_ACT_NONE && act != CCVPE_ACT_RELU) return fail(CCVPE_EINVAL, "up2: activation");
+// `id`: up2_supported()'s answer for `d`, which the caller's gate (up_pick, upconv_impl.h) has accepted
+int up2_launch(int id, const ccvpe_upconv_desc* d, hipStream_t stream) {
   Up2Params q{};
-  q.src0 = src0; q.src1 = src1; q.w = w; q.shift9 = shift9; q.dst = dst;
-  if (n % 8 || ldd % 8) return fail(CCVPE_EINVAL, "up2: n and ldd must be multiples of 8");
-  q.H1 = h1; q.W1 = w1; q.ld0 = ld0; q.ld1 = ld1; q.N = n; q.Npad = (n + 15) / 16 * 16; q.Kpad = kpad; q.ldd = ldd;
-  q.act_floor = act == CCVPE_ACT_RELU ? 0.f : -__builtin_huge_valf();
-  if (id == 1) return launch_up2<11, 2, 3, 8>(q, batch, stream);
-  if (id == 2) return launch_up2<8, 2, 2, 8>(q, batch, stream);
-  return launch_up2<17, 2, 2, 8>(q, batch, stream);
+  q.src0 = d->src0; q.src1 = d->src1; q.w = d->w; q.shift9 = d->shift9; q.dst = d->dst;
+  q.H1 = d->h1; q.W1 = d->w1; q.ld0 = d->ld0; q.ld1 = d->ld1; q.N = d->n; q.Npad = (d->n + 15) / 16 * 16; q.Kpad = d->kpad; q.ldd = d->ldd;
+  q.act_floor = d->act == CCVPE_ACT_RELU ? 0.f : -__builtin_huge_valf();
+  if (id == 1) return launch_up2<11, 2, 3, 8>(q, d->batch, stream);
+  if (id == 2) return launch_up2<8, 2, 2, 8>(q, d->batch, stream);
+  if (id == 3) return launch_up2<17, 2, 2, 8>(q, d->batch, stream);
+  return fail(CCVPE_EINVAL, "up2: unsupported layer");
 }
 
 }  // namespace ccvpe

@@ -889,71 +889,9 @@ __global__ __launch_bounds__(256, 2) void upconv_dma_kernel(const UpParams p) {
   CCVPE_ACT_DISPATCH(p.act, epilogue);
 }
 
-// route (optional): CCVPE_UPROUTE_* | MT << 8 | NT << 12 | WN << 16 of the kernel that WOULD run; nothing is launched
-template <typename T, int MT, int NT, int WN>
-static int launch_up(const UpParams& p0, hipStream_t stream, int* route = nullptr) {
-  constexpr int WM = 4 / WN;
-  constexpr int BM = 16 * MT * WM;
-  constexpr int BN = 16 * NT * WN;
-  constexpr int TH = BM / 16;
-  UpParams p = p0;
-  p.tiles_n = (p.Npad + BN - 1) / BN;
-  const int batch = p.M / (p.H1 * p.W1);
-  // The halo kernel tiles the low-res image in TH x 16 pixel tiles: with W1 < 16 (level 6: 8x8) half of
-  // every MFMA pixel tile would be padding, so those shapes use the linear-M gather kernel.
-  const bool halo = p.W1 >= 16;
-  p.tiles_m = halo ? ((p.W1 + 15) / 16) * ((p.H1 + TH - 1) / TH) * batch : (p.M + BM - 1) / BM;
-  const long total = (long)p.tiles_m * p.tiles_n * 4;
-  if (total > 0x7fffffffL) return fail(CCVPE_EINVAL, "upconv: grid too large");
-  p.tiles_total = (int)total;
-  {
-    // bf16: pair-of-taps stages with W by LDS-DMA (see upconv_dma_kernel) where the DMA's preconditions hold; fp32 (where the
-    // kernel measured the same as upconv_halo_kernel, +-3 %) only for level 6, whose alternative is the linear-M gather kernel
-    // (the 256 x 48 tile measured slower with it, 479 -> 531 us at N = 40, also with three workgroups per SIMD forced: 505)
-    // Every 64-byte panel row the DMA reads must lie inside its W row: phase A reads K columns up to 3 c0 + ceil32(c0) (the last
-    // tap's last, partly empty chunk: with c1 = 0 and c0 % 32 != 0 that crosses the row end — the reads of VALID K columns would
-    // then have to be shifted, so such shapes stay on upconv_halo_kernel); phase B starts at 4 c0 = 0 mod 32 and ends inside Kpad.
-    constexpr int SKL = 4 * ElemTraits<T>::E;
-    const bool dma_ok = p.Npad % BN == 0 && 3 * p.c0 + (p.c0 + SKL - 1) / SKL * SKL <= p.Kpad && !(NT == 3 && WN == 1);
-    auto go = [&](auto pair_tag) -> int {
-      constexpr bool PAIR = decltype(pair_tag)::value;
-      using G = UpDmaGeom<T, MT, NT, WN, PAIR>;
-      static_assert(G::LDS_BYTES <= 80 * 1024, "upconv_dma_kernel: two workgroups per CU");
-      static DevCache lds_set;                      // per (T, tile, PAIR) instantiation
-      if (int rc = ensure_dyn_lds(lds_set, upconv_dma_kernel<T, MT, NT, WN, PAIR>, G::LDS_BYTES, "upconv_dma_kernel")) return rc;
-      hipLaunchKernelGGL((upconv_dma_kernel<T, MT, NT, WN, PAIR>), dim3(p.tiles_total), dim3(256), G::LDS_BYTES, stream, p);
-      return check_launch("upconv_dma_kernel");
-    };
-    const int tile_bits = (MT << 8) | (NT << 12) | (WN << 16);
-    if constexpr (sizeof(T) == 2) {
-      if (halo && dma_ok) {
-        if (route) { *route = CCVPE_UPROUTE_DMA | tile_bits; return CCVPE_OK; }
-        return go(std::false_type{});
-      }
-    }
-    if constexpr (MT == 4 && NT == 5 && WN == 2) {
-      // level 6 (8 x 8 low-res images): two images per 8 x 16 tile instead of the linear-M gather kernel
-      if (dma_ok && p.W1 == 8 && p.H1 == TH) {
-        if (route) { *route = CCVPE_UPROUTE_DMA_PAIR | tile_bits; return CCVPE_OK; }
-        p.tiles_m = (batch + 1) / 2;
-        p.tiles_total = p.tiles_m * p.tiles_n * 4;
-        return go(std::true_type{});
-      }
-    }
-    if (route) { *route = (halo ? CCVPE_UPROUTE_HALO : CCVPE_UPROUTE_GATHER) | tile_bits; return CCVPE_OK; }
-  }
-  if (halo)
-    hipLaunchKernelGGL((upconv_halo_kernel<T, MT, NT, WN>), dim3(p.tiles_total), dim3(256), 0, stream, p);
-  else
-    hipLaunchKernelGGL((upconv_kernel<T, MT, NT, WN>), dim3(p.tiles_total), dim3(256), 0, stream, p);
-  return check_launch("upconv_kernel");
-}
-
-
-int upconv_route_f32(const ccvpe_upconv_desc* d, int* route);     // upconv_f32.hip (the fp32 instantiations live there)
-
+// Validates `d` and fills the kernels' parameter block (nothing about tiles); both entry points below start here.
 template <typename T>
-static int upconv_any(const ccvpe_upconv_desc* d, void* stream, int* route = nullptr) {
+static int up_fill(const ccvpe_upconv_desc* d, UpParams& p) {
   constexpr int E = ElemTraits<T>::E;
   constexpr int SK = 4 * E;
   constexpr int CPS = SK / 8;
@@ -964,7 +902,6 @@ static int upconv_any(const ccvpe_upconv_desc* d, void* stream, int* route = nul
   if (!aligned16(d->src0) || (d->src1 && !aligned16(d->src1)) || !aligned16(d->w) || !aligned16(d->dst))
     return fail(CCVPE_EINVAL, "upconv: pointers must be 16-byte aligned");
   if (!d->shift9) return fail(CCVPE_EINVAL, "upconv: shift9 required");
-  UpParams p;
   p.src0 = d->src0; p.src1 = d->src1; p.w = d->w; p.shift9 = d->shift9; p.dst = d->dst;
   p.out_f32 = sizeof(T) == 4;
   p.c0 = d->c0; p.ld0 = d->ld0; p.c1 = d->c1; p.ld1 = d->ld1;
@@ -978,24 +915,100 @@ static int upconv_any(const ccvpe_upconv_desc* d, void* stream, int* route = nul
   const long M = (long)d->batch * d->h1 * d->w1;
   if (M <= 0 || 4 * M > 0x7fffffffL) return fail(CCVPE_EINVAL, "upconv: bad M");
   p.M = (int)M;
-  p.tiles_n = p.tiles_m = p.tiles_total = 0;
-  hipStream_t st = (hipStream_t)stream;
-  if constexpr (sizeof(T) == 2) {
-    // the narrow levels: all four parities of a low-res tile in one workgroup, weights in registers (narrow_impl.h)
-    if (g_use_narrow && d->c1 > 0 && d->ldd % 8 == 0 && d->n % 8 == 0 && (d->act == CCVPE_ACT_NONE || d->act == CCVPE_ACT_RELU) &&
-        up2_supported(d->c0, d->c1, d->n, d->kpad, d->h1, d->w1, d->batch)) {
-      if (route) { *route = CCVPE_UPROUTE_UP2; return CCVPE_OK; }
-      return up2_dispatch(d->src0, d->src1, d->w, d->shift9, d->dst, d->c0, d->ld0, d->c1, d->ld1, d->h1, d->w1, d->n, d->kpad,
-                          d->ldd, d->act, d->batch, st);
-    }
-  }
+  return CCVPE_OK;      // (the grid: up_pick)
+}
+
+// ---- the route: up_pick() alone knows the order up2, DMA, DMA-pair, halo, gather; the launch and ccvpe_upconv3x3_route go through it.
+// kind: CCVPE_UPROUTE_* (the ABI encodes kind | mt << 8 | nt << 12 | wn << 16); up2 has no tile but up2_supported()'s instantiation id
+struct UpRoute { int kind, mt, nt, wn, up2_id; };
+
+// The tiles upconv_dma_kernel exists for.  Non-pair: bf16 only (fp32 measured the same as upconv_halo_kernel, +-3 %), not the 256 x 48 tile
+// (479 -> 531 us at N = 40, with three workgroups per SIMD forced 505).  Pair (level 6, instead of the gather kernel): 128 x 160, both types.
+constexpr bool up_dma_tile(int esz, int nt, int wn) { return esz == 2 && !(nt == 3 && wn == 1); }
+constexpr bool up_pair_tile(int mt, int nt, int wn) { return mt == 4 && nt == 5 && wn == 2; }
+
+// the route of a validated layer; writes the grid of that kind into `p`
+template <typename T>
+static int up_pick(const ccvpe_upconv_desc* d, UpParams& p, UpRoute& r) {
+  constexpr int esz = (int)sizeof(T);
+  r = UpRoute{};
+  // the narrow levels: all four parities of a low-res tile in one workgroup, weights in registers (narrow_impl.h)
+  if (esz == 2 && g_use_narrow && d->ldd % 8 == 0 && d->n % 8 == 0 && (d->act == CCVPE_ACT_NONE || d->act == CCVPE_ACT_RELU))
+    r.up2_id = up2_supported(d->c0, d->c1, d->n, d->kpad, d->h1, d->w1, d->batch);
+  if (r.up2_id) { r.kind = CCVPE_UPROUTE_UP2; return CCVPE_OK; }
   const TileCfg c = kCfgs[pick_cfg(p.Npad)];
+  r.mt = c.mt; r.nt = c.nt; r.wn = c.wn;
+  const int bm = 16 * c.mt * (4 / c.wn), bn = 16 * c.nt * c.wn, th = bm / 16;
+  // The halo kernels tile the low-res image in TH x 16 pixel tiles: with W1 < 16 (level 6: 8 x 8) half of every MFMA pixel tile
+  // would be padding, so those shapes use the linear-M gather kernel, or two images per 8 x 16 tile (pair).
+  const bool halo = p.W1 >= 16;
+  // The DMA has no row guard, and every 64-byte panel row it reads must lie inside its W row: phase A reads K columns up to
+  // 3 c0 + ceil32(c0) (the last tap's last, partly empty chunk: with c1 = 0 and c0 % 32 != 0 that crosses the row end, so such shapes
+  // stay on upconv_halo_kernel); phase B starts at 4 c0 = 0 mod 32 and ends inside Kpad.
+  constexpr int SKL = 4 * ElemTraits<T>::E;
+  const bool dma_ok = p.Npad % bn == 0 && 3 * p.c0 + (p.c0 + SKL - 1) / SKL * SKL <= p.Kpad;
+  if (halo && dma_ok && up_dma_tile(esz, c.nt, c.wn)) r.kind = CCVPE_UPROUTE_DMA;
+  else if (dma_ok && up_pair_tile(c.mt, c.nt, c.wn) && p.W1 == 8 && p.H1 == th) r.kind = CCVPE_UPROUTE_DMA_PAIR;
+  else r.kind = halo ? CCVPE_UPROUTE_HALO : CCVPE_UPROUTE_GATHER;
+  p.tiles_n = (p.Npad + bn - 1) / bn;
+  const long tiles_m = r.kind == CCVPE_UPROUTE_DMA_PAIR ? (d->batch + 1) / 2
+                       : halo ? (long)((p.W1 + 15) / 16) * ((p.H1 + th - 1) / th) * d->batch : (p.M + bm - 1) / bm;
+  const long total = tiles_m * p.tiles_n * 4;
+  if (total > 0x7fffffffL) return fail(CCVPE_EINVAL, "upconv: grid too large");
+  p.tiles_m = (int)tiles_m; p.tiles_total = (int)total;
+  return CCVPE_OK;
+}
+
+template <typename T, int MT, int NT, int WN, bool PAIR>
+static int launch_up_dma(const UpParams& p, hipStream_t stream) {
+  using G = UpDmaGeom<T, MT, NT, WN, PAIR>;
+  static_assert(G::LDS_BYTES <= 80 * 1024, "upconv_dma_kernel: two workgroups per CU");
+  static DevCache lds_set;                      // per (T, tile, PAIR) instantiation
+  if (int rc = ensure_dyn_lds(lds_set, upconv_dma_kernel<T, MT, NT, WN, PAIR>, G::LDS_BYTES, "upconv_dma_kernel")) return rc;
+  hipLaunchKernelGGL((upconv_dma_kernel<T, MT, NT, WN, PAIR>), dim3(p.tiles_total), dim3(256), G::LDS_BYTES, stream, p);
+  return check_launch("upconv_dma_kernel");
+}
+
+// the kernel of `kind` on one tile; the DMA forms exist for the tiles up_pick() routes to them and no others
+template <typename T, int MT, int NT, int WN>
+static int launch_up(const UpParams& p, int kind, hipStream_t stream) {
+  switch (kind) {
+    case CCVPE_UPROUTE_DMA:
+      if constexpr (up_dma_tile((int)sizeof(T), NT, WN)) return launch_up_dma<T, MT, NT, WN, false>(p, stream);
+      break;
+    case CCVPE_UPROUTE_DMA_PAIR:
+      if constexpr (up_pair_tile(MT, NT, WN)) return launch_up_dma<T, MT, NT, WN, true>(p, stream);
+      break;
+    case CCVPE_UPROUTE_HALO:
+      hipLaunchKernelGGL((upconv_halo_kernel<T, MT, NT, WN>), dim3(p.tiles_total), dim3(256), 0, stream, p);
+      return check_launch("upconv_kernel");
+    case CCVPE_UPROUTE_GATHER:
+      hipLaunchKernelGGL((upconv_kernel<T, MT, NT, WN>), dim3(p.tiles_total), dim3(256), 0, stream, p);
+      return check_launch("upconv_kernel");
+  }
+  return fail(CCVPE_EINVAL, "upconv: no kernel of kind %d for this tile", kind);
+}
+
+template <typename T>
+static int upconv_run(const ccvpe_upconv_desc* d, void* stream) {
+  UpParams p; UpRoute r;
+  if (const int rc = up_fill<T>(d, p)) return rc;
+  if (const int rc = up_pick<T>(d, p, r)) return rc;
+  if (r.kind == CCVPE_UPROUTE_UP2) return up2_launch(r.up2_id, d, (hipStream_t)stream);
 #define CCVPE_CASE(MT_, NT_, WN_) \
-  if (c.mt == MT_ && c.nt == NT_ && c.wn == WN_) return launch_up<T, MT_, NT_, WN_>(p, st, route);
+  if (r.mt == MT_ && r.nt == NT_ && r.wn == WN_) return launch_up<T, MT_, NT_, WN_>(p, r.kind, (hipStream_t)stream);
   CCVPE_TILES(CCVPE_CASE)
 #undef CCVPE_CASE
   return fail(CCVPE_EINVAL, "upconv: no tile config");
 }
 
+// the encoded route of the launch upconv_run() would make; host arithmetic only
+template <typename T>
+static int upconv_route(const ccvpe_upconv_desc* d) {
+  UpParams p; UpRoute r;
+  if (const int rc = up_fill<T>(d, p)) return rc;
+  if (const int rc = up_pick<T>(d, p, r)) return rc;
+  return r.kind | (r.mt << 8) | (r.nt << 12) | (r.wn << 16);
+}
 
 }  // namespace ccvpe

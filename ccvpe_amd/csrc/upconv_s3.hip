@@ -361,28 +361,50 @@ static int launch_s3(UpS3Params p, hipStream_t stream) {
   return check_launch("upconv_s3_kernel");
 }
 
-// the tile families the kernel is instantiated for (rows of kCfgs)
-static bool s3_tile(int mt, int nt, int wn) {
-  return mt == 4 && ((wn == 2 && (nt == 5 || nt == 4 || nt == 2 || nt == 1)) || (wn == 1 && (nt == 5 || nt == 3)));
-}
+// The tiles upconv_s3_kernel is instantiated for: a deliberate SUBSET of the tile table (CCVPE_TILES, conv_common.h), written once —
+// s3_pick() serves an n whose tile is in it, s3_run() launches from it.  X(MT, NT, WN) per row.
+#define CCVPE_S3_TILES(X) X(4, 5, 2) X(4, 4, 2) X(4, 2, 2) X(4, 1, 2) X(4, 5, 1) X(4, 3, 1)
 
-// nullptr if the kernel computes this layer, else why not
-static const char* s3_refusal(const ccvpe_upconv_desc* d) {
+// ---- the route: s3_pick() alone validates, decides the form and the tile; the three queries and the launch read its answer
+struct S3Route { int form, pair, mt, nt, wn; };      // form 1 = per-parity (pair: two 8 x 8 images per tile), 2 = quad (MT 2, NT = Npad / 16, WN 0)
+
+static bool g_s3_quad = true;                     // ccvpe_set_s3_quad
+
+// Size rule (measured per level at B = 64 with tools/up_probe.py).  profiles/r10/up_probe.txt: the three-plane kernel
+// beat ccvpe_upconv3x3_f32 in isolation on all ten decoder layers (1.32x at N = 40 to 1.72x at N = 128), every tile family.
+// profiles/r11/up_probe.txt: the quad form (upconv_s3q.hip) beat the per-parity kernel in isolation on all four levels it serves, by
+// more than the spread of the probe's repetitions (quad / per-parity 0.79 at N = 32, 0.81 at N = 40, 0.88 at N = 64, 0.96 at N = 80;
+// spreads 0.01-0.04).  The smallest of those layers has 4096 low-res pixels and nothing below that was measured, so smaller
+// problems keep the fp32 kernel (ccvpe_upconv3x3_s3_ok answers 1, not 2) and, asked for auto, the per-parity form.
+static bool s3_measured_size(const ccvpe_upconv_desc* d) { return (long)d->batch * d->h1 * d->w1 >= 4096; }
+
+// nullptr and the route if `form` (0 = auto) computes this layer, else why not
+static const char* s3_pick(const ccvpe_upconv_desc* d, int form, S3Route& r) {
+  r = S3Route{};
   if (!d) return "null desc";
   if (d->c0 <= 0 || d->c0 % 8 || d->c1 <= 0 || d->c1 % 8) return "c0 / c1 must be positive multiples of 8 (a layer without a skip is not implemented)";
   if (d->batch <= 0 || d->h1 <= 0 || d->w1 <= 0 || d->n <= 0) return "bad shape";
   if (d->ld0 < d->c0 || d->ld0 % 4 || d->ld1 < d->c1 || d->ld1 % 4 || d->ldd < d->n || d->ldd % 4) return "bad strides";
   const int nst = 4 * ((d->c0 + 15) / 16) + 9 * ((d->c1 + 15) / 16);
   if (d->kpad != nst * 48) return "kpad is not that of the three-plane pack (models._pack_upconv_s3)";
-  const bool pair = d->w1 == 8 && d->h1 == 8;
+  const bool pair = d->w1 == 8 && d->h1 == 8;      // level 6: two images side by side in one 8 x 16 tile
   if (d->w1 < 16 && !pair) return "low-res images narrower than 16 pixels (other than 8 x 8)";
   const int npad = (d->n + 15) / 16 * 16;
   const TileCfg c = kCfgs[pick_cfg(npad)];
-  if (!s3_tile(c.mt, c.nt, c.wn)) return "no tile for this n";
+  bool tile = false;
+#define CCVPE_CASE(MT_, NT_, WN_) tile = tile || (c.mt == MT_ && c.nt == NT_ && c.wn == WN_);
+  CCVPE_S3_TILES(CCVPE_CASE)
+#undef CCVPE_CASE
+  if (!tile) return "no tile for this n";
   if (pair && !(c.nt == 5 && c.wn == 2)) return "8 x 8 images need the 160-column tile";
   // 32-bit byte offsets into both sources, 31-bit pixel indices
   const double m = (double)d->batch * d->h1 * d->w1;
   if (m * d->ld0 * 4.0 >= 4294967296.0 || 4.0 * m * d->ld1 * 4.0 >= 4294967296.0 || 4.0 * m >= 2147483648.0) return "tensor too large";
+  if (form < 0 || form > 2) return "form must be 0 (auto), 1 (per-parity) or 2 (quad)";
+  const bool quad = upconv_s3q_serves(d);
+  if (form == 2 && !quad) return "the quad form serves 16 < n <= 80 and images of 16 or more pixels a row";
+  if (form == 0) form = g_s3_quad && quad && s3_measured_size(d) ? 2 : 1;
+  r = form == 2 ? S3Route{2, 0, 2, npad / 16, 0} : S3Route{1, pair, c.mt, c.nt, c.wn};
   return nullptr;
 }
 
@@ -390,25 +412,9 @@ static const char* s3_refusal(const ccvpe_upconv_desc* d) {
 
 using namespace ccvpe;
 
-// Size rule (measured per level at B = 64 with tools/up_probe.py; profiles/r10/up_probe.txt): the three-plane kernel
-// beat ccvpe_upconv3x3_f32 in isolation on all ten decoder layers (1.32x at N = 40 to 1.72x at N = 128), every tile family; the
-// smallest of them has 4096 low-res pixels, and nothing below that was measured, so smaller problems keep the fp32 kernel.
 extern "C" int ccvpe_upconv3x3_s3_ok(const ccvpe_upconv_desc* d) {
-  if (s3_refusal(d)) return 0;
-  const long m = (long)d->batch * d->h1 * d->w1;
-  return m >= 4096 ? 2 : 1;
-}
-
-// Which form computes a served desc when the caller leaves the choice to the library (form 0).  Measured per level at B = 64 with
-// tools/up_probe.py (profiles/r11/up_probe.txt): the quad form (upconv_s3q.hip) beat the per-parity kernel in
-// isolation on all four levels it serves, by more than the spread of the probe's repetitions (quad / per-parity 0.79 at N = 32,
-// 0.81 at N = 40, 0.88 at N = 64, 0.96 at N = 80; spreads 0.01-0.04); nothing below 4096 low-res pixels was measured, so smaller
-// problems keep the per-parity kernel.
-static bool g_s3_quad = true;                     // ccvpe_set_s3_quad
-static int s3_auto_form(const ccvpe_upconv_desc* d) {
-  if (!g_s3_quad || !upconv_s3q_serves(d)) return 1;
-  const long m = (long)d->batch * d->h1 * d->w1;
-  return m >= 4096 ? 2 : 1;
+  S3Route r;
+  return s3_pick(d, 1, r) ? 0 : s3_measured_size(d) ? 2 : 1;
 }
 
 extern "C" int ccvpe_set_s3_quad(int on) {
@@ -418,37 +424,30 @@ extern "C" int ccvpe_set_s3_quad(int on) {
 }
 
 extern "C" int ccvpe_upconv3x3_s3_form_ok(const ccvpe_upconv_desc* d, int form) {
-  if (s3_refusal(d)) return 0;
-  if (form == 0) return s3_auto_form(d);
-  if (form == 1) return 1;
-  if (form == 2) return upconv_s3q_serves(d) ? 2 : 0;
-  return 0;
+  S3Route r;
+  return s3_pick(d, form, r) ? 0 : r.form;
+}
+
+extern "C" int ccvpe_upconv3x3_s3_route(const ccvpe_upconv_desc* d, int form) {
+  S3Route r;
+  return s3_pick(d, form, r) ? 0 : r.form | (r.pair << 4) | (r.mt << 8) | (r.nt << 12) | (r.wn << 16);
 }
 
 static int s3_run(const ccvpe_upconv_desc* d, int form, void* stream) {
-  if (const char* why = s3_refusal(d)) return fail(CCVPE_EINVAL, "upconv3x3_s3: %s", why);
-  if (form < 0 || form > 2) return fail(CCVPE_EINVAL, "upconv3x3_s3: form must be 0 (auto), 1 (per-parity) or 2 (quad)");
+  S3Route r;
+  if (const char* why = s3_pick(d, form, r)) return fail(CCVPE_EINVAL, "upconv3x3_s3: %s", why);
   if (!d->src0 || !d->src1 || !d->w || !d->shift9 || !d->dst) return fail(CCVPE_EINVAL, "upconv3x3_s3: null pointer");
   if (!aligned16(d->src0) || !aligned16(d->src1) || !aligned16(d->w) || !aligned16(d->dst))
     return fail(CCVPE_EINVAL, "upconv3x3_s3: pointers must be 16-byte aligned");
-  if (form == 0) form = s3_auto_form(d);
-  if (form == 2) return upconv_s3q_launch(d, (hipStream_t)stream);       // (refuses a desc the quad form does not serve)
-  UpS3Params p;
-  p.src0 = reinterpret_cast<const float*>(d->src0); p.src1 = reinterpret_cast<const float*>(d->src1);
-  p.w = d->w; p.shift9 = d->shift9; p.dst = reinterpret_cast<float*>(d->dst);
-  p.c0 = d->c0; p.ld0 = d->ld0; p.c1 = d->c1; p.ld1 = d->ld1;
-  p.H1 = d->h1; p.W1 = d->w1; p.batch = d->batch;
-  p.N = d->n; p.Npad = (d->n + 15) / 16 * 16;
-  p.nb0 = (d->c0 + 15) / 16; p.nb1 = (d->c1 + 15) / 16; p.nst = 4 * p.nb0 + 9 * p.nb1;
-  p.ldd = d->ldd; p.act = d->act;
-  p.tiles_n = p.tiles_total = 0;
   hipStream_t st = (hipStream_t)stream;
-  const TileCfg c = kCfgs[pick_cfg(p.Npad)];
-  if (d->w1 == 8 && d->h1 == 8) return launch_s3<4, 5, 2, true>(p, st);
+  if (r.form == 2) return upconv_s3q_launch(d, st);
+  UpS3Params p;
+  s3_fill(d, p);
+  p.Npad = (d->n + 15) / 16 * 16;      // (tiles_n, tiles_total: launch_s3)
+  if (r.pair) return launch_s3<4, 5, 2, true>(p, st);      // (s3_pick: a pair layer has the 160-column tile)
 #define CCVPE_CASE(MT_, NT_, WN_) \
-  if (c.mt == MT_ && c.nt == NT_ && c.wn == WN_) return launch_s3<MT_, NT_, WN_, false>(p, st);
-  // a deliberate SUBSET of the tile table (CCVPE_TILES, conv_common.h): the rows s3_tile() accepts, kept as an explicit list
-  CCVPE_CASE(4, 5, 2) CCVPE_CASE(4, 4, 2) CCVPE_CASE(4, 2, 2) CCVPE_CASE(4, 1, 2) CCVPE_CASE(4, 5, 1) CCVPE_CASE(4, 3, 1)
+  if (r.mt == MT_ && r.nt == NT_ && r.wn == WN_) return launch_s3<MT_, NT_, WN_, false>(p, st);
+  CCVPE_S3_TILES(CCVPE_CASE)
 #undef CCVPE_CASE
   return fail(CCVPE_EINVAL, "upconv3x3_s3: no tile config");
 }

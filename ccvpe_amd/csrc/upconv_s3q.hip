@@ -336,36 +336,32 @@ template <int NT>
 static int launch_s3q(UpS3qParams p, hipStream_t stream) {
   using G = UpS3qGeom<NT>;
   static_assert(G::LDS_BYTES <= 80 * 1024, "upconv_s3q_kernel: two workgroups per CU");
-  p.tiles_total = ((p.W1 + 15) / 16) * ((p.H1 + G::TH - 1) / G::TH) * p.batch;      // < 2^31: s3_refusal bounds the pixel count
+  p.tiles_total = ((p.W1 + 15) / 16) * ((p.H1 + G::TH - 1) / G::TH) * p.batch;      // < 2^31: s3_pick() bounds the pixel count
   static DevCache lds_set;                      // per instantiation
   if (int rc = ensure_dyn_lds(lds_set, upconv_s3q_kernel<NT>, G::LDS_BYTES, "upconv_s3q_kernel")) return rc;
   hipLaunchKernelGGL((upconv_s3q_kernel<NT>), dim3(p.tiles_total), dim3(256), G::LDS_BYTES, stream, p);
   return check_launch("upconv_s3q_kernel");
 }
 
-// the quad form's own shape conditions, for a desc upconv_s3.hip's s3_refusal has accepted
+// The NT = Npad / 16 the kernel is instantiated for, written once: the quad form's N range (16 < n <= 80) and its launch.
+#define CCVPE_S3Q_NTS(X) X(2) X(3) X(4) X(5)
+
+// the quad form's own shape conditions, for a desc upconv_s3.hip's s3_pick() has accepted
 bool upconv_s3q_serves(const ccvpe_upconv_desc* d) {
-  const int npad = (d->n + 15) / 16 * 16;
-  return d->w1 >= 16 && npad >= 32 && npad <= 80;
+  const int nt = (d->n + 15) / 16;
+#define CCVPE_CASE(NT_) if (nt == NT_) return d->w1 >= 16;
+  CCVPE_S3Q_NTS(CCVPE_CASE)
+#undef CCVPE_CASE
+  return false;
 }
 
 int upconv_s3q_launch(const ccvpe_upconv_desc* d, hipStream_t stream) {
-  if (!upconv_s3q_serves(d)) return fail(CCVPE_EINVAL, "upconv3x3_s3: the quad form serves 16 < n <= 80 and images of 16 or more pixels a row");
   UpS3qParams p;
-  p.src0 = reinterpret_cast<const float*>(d->src0); p.src1 = reinterpret_cast<const float*>(d->src1);
-  p.w = d->w; p.shift9 = d->shift9; p.dst = reinterpret_cast<float*>(d->dst);
-  p.c0 = d->c0; p.ld0 = d->ld0; p.c1 = d->c1; p.ld1 = d->ld1;
-  p.H1 = d->h1; p.W1 = d->w1; p.batch = d->batch;
-  p.N = d->n;
-  p.nb0 = (d->c0 + 15) / 16; p.nb1 = (d->c1 + 15) / 16; p.nst = 4 * p.nb0 + 9 * p.nb1;
-  p.ldd = d->ldd; p.act = d->act;
-  p.tiles_total = 0;
-  switch ((d->n + 15) / 16) {
-    case 2: return launch_s3q<2>(p, stream);
-    case 3: return launch_s3q<3>(p, stream);
-    case 4: return launch_s3q<4>(p, stream);
-    case 5: return launch_s3q<5>(p, stream);
-  }
+  s3_fill(d, p);
+  const int nt = (d->n + 15) / 16;
+#define CCVPE_CASE(NT_) if (nt == NT_) return launch_s3q<NT_>(p, stream);
+  CCVPE_S3Q_NTS(CCVPE_CASE)
+#undef CCVPE_CASE
   return fail(CCVPE_EINVAL, "upconv3x3_s3: no quad tile");
 }
 

@@ -55,7 +55,7 @@ class LaunchRecorder(object):
 
 
 def igemm_tile(n, is3x3=False):
-    """Mirror of pick_cfg() in csrc/conv_igemm.hip: (BM, BN) chosen for a GEMM N (reporting only)."""
+    """Mirror of pick_cfg() in csrc/conv_igemm.hip: (BM, BN) chosen for a GEMM N (reporting only: the split-K launch's name)."""
     npad = (n + 15) // 16 * 16
     cfgs = [(4, 5, 2), (4, 4, 2), (4, 3, 2), (4, 2, 2), (4, 1, 2), (4, 5, 1), (4, 3, 1), (4, 1, 1), (2, 7, 1)]
     best, best_cost = None, None
@@ -112,6 +112,15 @@ def upconv_route_name(desc, is_bf16):
     if k == "up2_kernel":
         return "up2_kernel<bf16,%d,%d>" % (desc.c0, desc.n)
     return "%s<%s,%d,%d,%d%s>" % (k, ty, mt, nt, wn, ",pair" if pair else "")
+
+
+def upconv_s3_route_name(desc, form=0):
+    """The same for ccvpe_upconv3x3_s3_form_f32(desc, form): ccvpe_upconv3x3_s3_route, the library's own decision, no launch."""
+    r = _lib.load().ccvpe_upconv3x3_s3_route(ctypes.byref(desc), form)
+    if r <= 0:
+        raise _lib.CcvpeError("ccvpe_upconv3x3_s3_route: form %d does not compute this layer" % form)
+    mt, nt, wn = (r >> 8) & 0xf, (r >> 12) & 0xf, (r >> 16) & 0xf
+    return "upconv_s3q_kernel<%d,%d>" % (mt, nt) if r & 0xf == 2 else "upconv_s3_kernel<%d,%d,%d%s>" % (mt, nt, wn, ",pair" if r & 16 else "")
 
 
 def conv_route_name(desc, is_bf16, out_f32=False):
@@ -381,11 +390,7 @@ def upconv3x3_s3(src0, c0, w3_packed, shift9, n, *, batch, h1, w1, src1=None, c1
         k_eff = 4 * c0 + 9 * c1
         flops = 2.0 * m * n * k_eff
         nbytes = 4.0 * (batch * h1 * w1 * c0 + m * c1 + m * n + 4 * n * k_eff)
-        tile = igemm_tile(n).split("<")[1]
-        name = "upconv_s3_kernel<%s%s" % (tile[:-1], ",pair>" if (h1 == 8 and w1 == 8) else ">")
-        if lib.ccvpe_upconv3x3_s3_form_ok(ctypes.byref(d), form or 0) == 2:
-            name = "upconv_s3q_kernel<2,%d>" % ((n + 15) // 16)
-        rec.end(name, "up3x3 M%d N%d Keff%d" % (m, n, k_eff), flops, nbytes, ev0)
+        rec.end(upconv_s3_route_name(d, form or 0), "up3x3 M%d N%d Keff%d" % (m, n, k_eff), flops, nbytes, ev0)
     return dst
 
 

@@ -197,8 +197,12 @@ int ccvpe_upconv3x3_s3_f32(const ccvpe_upconv_desc* desc, void* stream);
  * ccvpe_upconv3x3_s3_form_ok launches nothing: 0 = `form` cannot compute the desc, else the form that runs (for form 0: what
  * auto picks, 1 or 2).  ccvpe_upconv3x3_s3_form_f32 forces a form (0 = auto) and returns CCVPE_EINVAL for one that cannot serve
  * the desc.  ccvpe_set_s3_quad(0) makes auto never choose form 2 (A/B runs; the binding calls it for CCVPE_S3_QUAD=0); the
- * forcing entry point ignores it.  Returns the previous setting. */
+ * forcing entry point ignores it.  Returns the previous setting.
+ * (ABI 7, additive) ccvpe_upconv3x3_s3_route launches nothing: the kernel ccvpe_upconv3x3_s3_form_f32(desc, form) would run, as
+ * form that runs | pair << 4 | MT << 8 | NT << 12 | WN << 16 (pair: the two-images-per-tile kernel of 8 x 8 layers; the quad form:
+ * MT = 2, NT = npad16 / 16, WN = 0), or 0 where _form_ok is 0.  For the launch recorder's names. */
 int ccvpe_upconv3x3_s3_form_ok(const ccvpe_upconv_desc* desc, int form);
+int ccvpe_upconv3x3_s3_route(const ccvpe_upconv_desc* desc, int form);
 int ccvpe_upconv3x3_s3_form_f32(const ccvpe_upconv_desc* desc, int form, void* stream);
 int ccvpe_set_s3_quad(int on);
 

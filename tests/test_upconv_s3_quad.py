@@ -42,8 +42,10 @@ def _slots():
 
 
 def test_instantiated_tiles_fit_two_workgroups_per_cu():
-    nts = sorted(int(v) for v in re.findall(r"case (\d): return launch_s3q<\1>", SRC))
+    # the one list the quad form's N range and its launch are generated from
+    nts = sorted(int(v) for v in re.findall(r"X\((\d)\)", re.search(r"#define CCVPE_S3Q_NTS\(X\)(.*)", SRC).group(1)))
     assert nts == [2, 3, 4, 5]
+    assert "if (nt == NT_) return launch_s3q<NT_>(p, stream);" in SRC and SRC.count("CCVPE_S3Q_NTS(CCVPE_CASE)") == 2
     assert "static_assert(G::LDS_BYTES <= 80 * 1024" in SRC
     for nt in nts:
         g = _geom(nt)
