@@ -26,7 +26,8 @@ and the 1 + 16 + 2 channel ground truth then run on the device exactly as for VI
 
 Oxford RobotCar (datasets.py:183-353): `OxfordPairs(grd_image_root, sat_path, split)` — list files + yaw fixtures, the UTM ->
 map-pixel fit, an 800 x 800 patch of the one large aerial map per sample; `DeviceBatches(pairs, B, grd_hw=(154, 231),
-ascending_bins=True)`.
+ascending_bins=True)`.  With `device_map=True` the map lives in HBM and the patches of a batch are cut, resized and normalised by
+ONE ccvpe_window_resize_norm_u8_f32 launch from a table of patch origins (bit-identical to the Pillow crop + resize).
 
 Sharding: DeviceBatches gives rank r a contiguous shard of the index list (after the optional seeded shuffle, identical on
 every rank).  Evaluation (`shard="exact"`): harness.shard_indices — no sample is seen twice, no collective is needed, ranks
@@ -294,6 +295,8 @@ OXFORD_UTM = ((619400., 5736195.), (619400., 5734600.), (620795., 5736195.), (62
 OXFORD_PIX = ((900., 900.), (492., 18168.), (15966., 1260.), (15553., 18528.), (8255., 9688.))
 OXFORD_LISTS = {"train": (("training.txt",), "train_yaw.npy"), "val": (("validation.txt",), "val_yaw.npy"),
                 "test": (("test1_j.txt", "test2_j.txt", "test3_j.txt"), "test_yaw.npy")}
+OXFORD_BOX = 800                            # side of the aerial patch in map pixels (datasets.py:300,317)
+OXFORD_MAP_MODES = ("RGB", "RGBA", "L")     # modes whose out-of-image crop fill converts to RGB (0, 0, 0)
 
 
 class OxfordPairs(object):
@@ -302,9 +305,19 @@ class OxfordPairs(object):
     around the vehicle plus a random offset of up to 200 * sqrt(2) map pixels (train: two draws from Python's `random` module,
     or from `rng`, a `random.Random`), or the half-overlapping grid patch that holds the vehicle at least 200 pixels from its
     border (val / test).  The Gaussian's centre is the vehicle's position in the 512 x 512 resized patch; the orientation bins of
-    this loader count UP (DeviceBatches(..., ascending_bins=True))."""
+    this loader count UP (DeviceBatches(..., ascending_bins=True)).
 
-    def __init__(self, grd_image_root, sat_path, split="train", rng=None):
+    device_map=True (opt-in) leaves the aerial side to the device: sample() cuts no patch (`sat_u8` is None) and returns the
+    patch's `sat_origin` = (x0, y0) on the map instead, keys() offers no aerial key in any split, and DeviceBatches serves the
+    whole aerial batch with ONE ccvpe_window_resize_norm_u8_f32 launch on the map resident in HBM (`map_on`), bit-identical
+    to the Pillow crop + resize.  Every draw and every other key is the same.  The map must be RGB, RGBA or L — the modes in
+    which the zero fill of a crop beyond the image converts to RGB (0, 0, 0), so converting the map once equals converting
+    each patch; any other mode (a palette's index 0 is a colour) raises ValueError.  The map is converted to RGB and uploaded
+    once per device, on the first batch for that device, and this index object owns the device copies.  The host keeps the
+    decoded Pillow image (`self.map`): the RGB array made for an upload is released right after it, and a second device
+    gets its own upload from the same host image (about 1 GB of HBM each for the real map)."""
+
+    def __init__(self, grd_image_root, sat_path, split="train", rng=None, device_map=False):
         from PIL import Image
         if split not in OXFORD_LISTS:
             raise ValueError("split must be 'train', 'val' or 'test'")
@@ -312,6 +325,11 @@ class OxfordPairs(object):
         Image.MAX_IMAGE_PIXELS = None                                  # the real map is 16 k x 19 k pixels
         self.map = Image.open(sat_path)
         self.map.load()
+        self.device_map = bool(device_map)
+        if self.device_map and self.map.mode not in OXFORD_MAP_MODES:
+            raise ValueError("device_map needs an aerial map of mode %s, %s is %r" % ("/".join(OXFORD_MAP_MODES), sat_path,
+                                                                                     self.map.mode))
+        self._map_dev, self._map_lock = {}, threading.Lock()
         files, yaw = OXFORD_LISTS[split]
         self.rows, self.list_lengths = [], []
         for fn in files:
@@ -358,17 +376,32 @@ class OxfordPairs(object):
             k -= 1
         return k, int(np.round(v - 400 * k))
 
+    def map_rgb(self):
+        """The map as the [H, W, 3] uint8 RGB array that device_map uploads (a fresh host array on every call)."""
+        return np.array(self.map.convert("RGB"))
+
+    def map_on(self, device):
+        """The RGB map as a [H, W, 3] uint8 tensor on `device`: uploaded on the first call for that device, then shared."""
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        with self._map_lock:
+            if device not in self._map_dev:
+                self._map_dev[device] = torch.from_numpy(self.map_rgb()).to(device)
+            return self._map_dev[device]
+
     def keys(self, idx, draws):
         """Sources of sample idx for a device image cache: the camera image's path and — val / test — "<map path>@<kc>,<kr>",
-        the grid patch; a training patch has a random offset: None."""
+        the grid patch; a training patch has a random offset: None.  device_map: the map serves the aerial side, None always."""
         sat = None
-        if self.split != "train":
+        if self.split != "train" and not self.device_map:
             col, row = self._position(idx)
             sat = "%s@%d,%d" % (self.sat_path, self._grid(col)[0], self._grid(row)[0])
         return {"grd": os.path.join(self.root, self.rows[idx][0]), "sat": sat}
 
     def sample(self, idx, sat_hw=(512, 512), grd_hw=(154, 231), draws=None, cached=None):
-        """cached: {side: raw (h, w)} of the sides a device image cache holds: not opened / cropped, their *_u8 entry is None."""
+        """cached: {side: raw (h, w)} of the sides a device image cache holds: not opened / cropped, their *_u8 entry is None.
+        device_map: no patch is cut, sat_u8 is None and `sat_origin` = (x0, y0) of the patch on the map is added."""
         from PIL import Image
         if cached is not None and "grd" in cached:
             grd = None
@@ -388,12 +421,16 @@ class OxfordPairs(object):
             box = (kc * 400, kr * 400, kc * 400 + 800, kr * 400 + 800)
             cy = int(-(pr / 800 * 512 - 256))
             cx = int(-(pc / 800 * 512 - 256))
-        sat = None if cached is not None and "sat" in cached else np.array(self.map.crop(box).convert("RGB"))
+        aerial = {}
+        if self.device_map:
+            sat, aerial = None, {"sat_origin": (int(box[0]), int(box[1]))}
+        else:
+            sat = None if cached is not None and "sat" in cached else np.array(self.map.crop(box).convert("RGB"))
         angle = float(self.yaw[idx]) / np.pi * 180 - 90                          # 0 = north, clockwise (datasets.py:334-337)
         if angle < 0:
             angle += 360
         return dict(grd_u8=grd, sat_u8=sat, roll=0, angle_deg=float(angle), center=(float(cx), float(cy)), city="oxford",
-                    index=int(idx))
+                    index=int(idx), **aerial)
 
 
 def shard_positions(n, world, rank, mode="exact"):
@@ -453,7 +490,11 @@ class DeviceBatches(object):
     inserts the misses (a key once per batch) and assembles each side of the batch with ONE ccvpe_gather_norm_u8_f32 launch
     over a table of slot addresses.  Sides without a key (KITTI's aligned crop, Oxford's training patch), blank panoramas and
     the misses of a full cache go through the cache's scratch slots and the same launch.  Draws are made in the same order and
-    the batches are bit-identical to those without a cache."""
+    the batches are bit-identical to those without a cache.
+
+    OxfordPairs(device_map=True): the aerial side of every batch, with or without a cache, is ONE
+    ccvpe_window_resize_norm_u8_f32 launch on the index's device-resident map over a [B, 2] table of patch origins, written
+    straight into batch.sat (tables from `sat_hw`); it never touches the cache.  Bit-identical to device_map=False."""
 
     def __init__(self, pairs, batch_size, device="cuda", indices=None, shuffle=False, seed=0, rank=0, world=1, workers=8,
                  prefetch=2, grd_hw=(320, 640), sat_hw=(512, 512), fov=360, targets=True, n_bins=20, drop_last=False,
@@ -568,6 +609,12 @@ class DeviceBatches(object):
         rows = torch.from_numpy(np.stack([s["align"] for s in samples])).to(self.device)
         return align.kitti_align(src, torch.from_numpy(offsets[:-1].copy()).to(self.device), rows, (KITTI_CROP, KITTI_CROP))
 
+    def _window_side(self, samples, dst):
+        """OxfordPairs(device_map=True): the aerial side of a batch = the origins table + ONE launch on the resident map."""
+        from . import preprocess
+        origins = torch.tensor([s["sat_origin"] for s in samples], dtype=torch.int32, device=self.device)
+        preprocess.window_resize_norm(self.pairs.map_on(self.device), origins, (OXFORD_BOX, OXFORD_BOX), self.sat_hw, dst=dst)
+
     def _to_device(self, samples):
         from . import preprocess, targets
         dev = self.device
@@ -576,15 +623,21 @@ class DeviceBatches(object):
         out.grd = torch.empty((b, 3, self.grd_hw[0], self.keep_w), device=dev, dtype=torch.float32)
         out.sat = torch.empty((b, 3) + self.sat_hw, device=dev, dtype=torch.float32)
         crops = self._align_on_device(samples) if b and "align" in samples[0] else None
+        window = bool(b) and "sat_origin" in samples[0]       # the aerial side comes from a device-resident map
         if self.cache is not None:
             self._gather_side(samples, "grd", self.grd_hw, self.keep_w, out.grd)
-            self._gather_side(samples, "sat", self.sat_hw, self.sat_hw[1], out.sat, crops=crops)
+            if not window:
+                self._gather_side(samples, "sat", self.sat_hw, self.sat_hw[1], out.sat, crops=crops)
         else:
             for i, s in enumerate(samples):
                 g = torch.from_numpy(s["grd_u8"]).to(dev, non_blocking=True)
-                a = torch.from_numpy(s["sat_u8"]).to(dev, non_blocking=True) if crops is None else crops[i]
+                if not window:
+                    a = torch.from_numpy(s["sat_u8"]).to(dev, non_blocking=True) if crops is None else crops[i]
                 preprocess.preprocess(g, self.grd_hw, dst=out.grd[i], roll=s["roll"], keep_w=self.keep_w)
-                preprocess.preprocess(a, self.sat_hw, dst=out.sat[i])
+                if not window:
+                    preprocess.preprocess(a, self.sat_hw, dst=out.sat[i])
+        if window:
+            self._window_side(samples, out.sat)
         out.angle_deg = torch.tensor([s["angle_deg"] for s in samples], device=dev, dtype=torch.float32)
         out.heading_deg = torch.tensor([s["angle_deg"] for s in samples], device=dev, dtype=torch.float64)
         out.center = torch.tensor([s["center"] for s in samples], device=dev, dtype=torch.float32)

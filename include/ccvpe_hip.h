@@ -705,6 +705,27 @@ int ccvpe_gather_norm_u8_f32(const long long* srcs, const int* rolls, int batch,
                              const float* mean, const float* stdv, float* dst, void* stream);
 
 /* -------------------------------------------------------------------------------------------
+ * Device-resident aerial map (csrc/preprocess.hip; Oxford RobotCar, the reference's datasets.py:296-330: crop an 800 x 800
+ * patch of the one large map, Resize, ToTensor, Normalize): crop + Pillow-exact resize + normalise of a whole batch side in
+ * ONE launch, with neither the window nor the horizontal intermediate written to memory.
+ *   map [map_h][map_w][3] uint8 (device; any size — every byte offset is 64-bit); origins [batch][2] int32 (device) =
+ *   (x0, y0) of each sample's box_h x box_w window, any sign, partly or wholly outside the map;
+ *   W_b[i][j][c] = map[y0 + i][x0 + j][c] inside the map, else 0 (PIL.Image.crop of an RGB image; never read outside);
+ *   dst [batch][3][out_h][out_w] fp32 = ccvpe_preprocess_u8_f32 of W_b (roll 0, keep_w = out_w), bit for bit.
+ *   Tables: ccvpe_amd/preprocess.py resample_tables(box_w, out_w) / (box_h, out_h) on the device; the ksize arguments must be
+ *   Pillow's for that geometry (2 * ceil(max(box / out, 1)) + 1), anything else is refused.  mean / std: HOST pointers.
+ *   batch == 0 succeeds without a launch (tables may be null); batch <= 65535 (grid z); out_h <= 65535 * 16.
+ *   Supported geometry: a 16 x 128 output tile stages floor(15 * box_h / out_h) + yksize + 1 window rows of 384 bytes in LDS
+ *   and that must fit in 64 KB (170 rows): any enlargement, equal size, and vertical reductions up to box_h / out_h of
+ *   about 9.8 (800 -> 512 stages 29 rows, a reduction by 4 stages 70); the horizontal factor is not limited.  A geometry
+ *   beyond that is refused with CCVPE_EINVAL before anything is launched.
+ * ----------------------------------------------------------------------------------------- */
+int ccvpe_window_resize_norm_u8_f32(const unsigned char* map, int map_h, int map_w, const int* origins, int batch, int box_h,
+                                    int box_w, const int* xbounds, const int* xcoef, int xksize, const int* ybounds,
+                                    const int* ycoef, int yksize, const float* mean, const float* stdv, float* dst, int out_h,
+                                    int out_w, void* stream);
+
+/* -------------------------------------------------------------------------------------------
  * KITTI aerial alignment (csrc/align.hip; the reference's datasets.py:443-464 / :577-596): PIL's rotate (NEAREST, 16.16
  * fixed point) -> two BILINEAR translations (float64, truncated) -> rotate -> centre crop, evaluated lazily per pixel
  * of the crop, bit-identical to Pillow.  ONE launch per batch.
