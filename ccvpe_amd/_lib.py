@@ -100,6 +100,9 @@ PROTOTYPES = {
     "ccvpe_upconv3x3_s3_route": (c_int, [ctypes.POINTER(UpconvDesc), c_int]),
     "ccvpe_upconv3x3_s3_form_f32": (c_int, [ctypes.POINTER(UpconvDesc), c_int, c_void_p]),
     "ccvpe_set_s3_quad": (c_int, [c_int]),
+    "ccvpe_pw_s3_ok": (c_int, [ctypes.POINTER(ConvDesc)]),
+    "ccvpe_pw_s3_route": (c_int, [ctypes.POINTER(ConvDesc)]),
+    "ccvpe_pw_s3_f32": (c_int, [ctypes.POINTER(ConvDesc), c_void_p]),
     "ccvpe_stem_conv_f32": (c_int, [c_void_p] * 5 + [c_int] * 4 + [c_void_p]),
     "ccvpe_dwconv_nblk": (c_int, [c_int] * 4),
     "ccvpe_dwconv_f32": (c_int, [c_void_p] * 6 + [c_int] * 7 + [c_void_p]),

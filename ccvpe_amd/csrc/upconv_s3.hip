@@ -25,7 +25,7 @@
 // Non-finite and overflowing inputs behave differently from the fp32 kernel: Inf splits into (Inf, NaN, NaN), |v| above 3.39e38
 // rounds hi to Inf, and bf16-subnormal planes (|v| below ~1e-38 x 2^16) may be flushed by the matrix unit.  The forward never
 // produces such values.
-#include "conv_common.h"
+#include "split3_impl.h"      // split3, store_planes, the fragment offsets
 
 namespace ccvpe {
 
@@ -57,34 +57,6 @@ struct UpS3Geom {
   static constexpr int WBUF_DW = W_INSTR * 256;
   static constexpr int LDS_BYTES = (U_DW + 2 * WBUF_DW) * 4;
 };
-
-__device__ __forceinline__ unsigned pk_bf16(float a, float b) {      // round-to-nearest-even pair (v_cvt_pk_bf16_f32)
-  typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-  bf16x2_t v;
-  v[0] = (__bf16)a;
-  v[1] = (__bf16)b;
-  return __builtin_bit_cast(unsigned, v);
-}
-__device__ __forceinline__ float bf_lo(unsigned p) { return __builtin_bit_cast(float, p << 16); }
-__device__ __forceinline__ float bf_hi(unsigned p) { return __builtin_bit_cast(float, p & 0xffff0000u); }
-
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-// four fp32 values -> their hi / mid / lo bf16 planes (4 bf16 = 8 bytes each)
-__device__ __forceinline__ void split3(f32x4 v, u32x2& hi, u32x2& mid, u32x2& lo) {
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    float a = v[2 * h], b = v[2 * h + 1];
-    const unsigned ph = pk_bf16(a, b);
-    a -= bf_lo(ph);
-    b -= bf_hi(ph);
-    const unsigned pm = pk_bf16(a, b);
-    a -= bf_lo(pm);
-    b -= bf_hi(pm);
-    hi[h] = ph;
-    mid[h] = pm;
-    lo[h] = pk_bf16(a, b);
-  }
-}
 
 template <int MT, int NT, int WN, bool PAIR>
 __global__ __launch_bounds__(256, 2) void upconv_s3_kernel(const UpS3Params p) {
@@ -153,13 +125,6 @@ __global__ __launch_bounds__(256, 2) void upconv_s3_kernel(const UpS3Params p) {
       h_keep |= ok ? (1u << it) : 0u;
     }
   };
-  auto store_planes = [&](float* at, f32x4 v) {
-    u32x2 hi, mid, lo;
-    split3(v, hi, mid, lo);
-    *reinterpret_cast<u32x2*>(at) = hi;
-    *reinterpret_cast<u32x2*>(at + 8) = mid;
-    *reinterpret_cast<u32x2*>(at + 16) = lo;
-  };
   auto store_halo = [&]() {
 #pragma unroll
     for (int it = 0; it < H_IT; ++it)
@@ -197,7 +162,8 @@ __global__ __launch_bounds__(256, 2) void upconv_s3_kernel(const UpS3Params p) {
     for (int j = 0; j < NT; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
   const int frow = lane & 15;
   const int g4 = lane >> 4;
-  // per-lane dword offsets of the fragments inside a 24-dword [hi|mid|lo] row
+  // per-lane dword offsets of the fragments inside a 24-dword [hi|mid|lo] row (S3Frag of split3_impl.h holds the same five for
+  // pw_s3.hip; they stay spelled out here because tests/test_upconv_s3.py reads them from this file for its bank model)
   const int a1off = 4 * g4;                                  // [x_hi | x_mid]
   const int a2off = g4 < 2 ? 16 + 4 * g4 : 4 * g4 - 8;       // [x_lo | x_hi ]
   const int w1off = 4 * (g4 & 1);                            // [w_hi | w_hi ]

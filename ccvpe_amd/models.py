@@ -114,9 +114,29 @@ class _Obj(object):
     pass
 
 
-def _pack_encoder(sd, p, dtype=torch.float32, fold_bn=True):
+def _pack_pw_s3(w):
+    """The fp32 pack [N^16][K] of _pack_conv / _pad2 (a 1x1 layer, or the 2x2 stride-2 descriptor with k = (ky * 2 + kx) * c0 + ch)
+    -> the three-bf16-plane pack of ccvpe_pw_s3_f32 (csrc/pw_s3.hip): [stage = k / 16][N^16][hi 16 | mid 16 | lo 16] bf16, the
+    planes of _split3_bf16 (hi + mid + lo == the fp32 weight exactly).  None for anything but an fp32 pack with K % 16 == 0."""
+    if w is None or w.dtype != torch.float32 or w.dim() != 2 or w.shape[1] % 16 or w.shape[0] % 16:
+        return None
+    npad, k = w.shape
+    return torch.cat(_split3_bf16(w.reshape(npad, k // 16, 16).permute(1, 0, 2)), -1).contiguous()
+
+
+def _unpack_pw_s3(w3):
+    """Inverse of _pack_pw_s3's layout: the three planes [N^16][K] in fp32 (their sum is the packed weight)."""
+    nst, npad, _ = w3.shape
+    return tuple(w3[..., 16 * q:16 * q + 16].float().permute(1, 0, 2).reshape(npad, nst * 16) for q in range(3))
+
+
+# block projections from this expanded width on get a three-plane pack (blocks 4-15; block 4, 240 -> 40, is not served: N <= 48)
+PW_S3_MIN_MID = 240
+
+
+def _pack_encoder(sd, p, dtype=torch.float32, fold_bn=True, s3=False):
     """fold_bn=False (train mode): BatchNorm uses batch statistics, the folded scale/shift would be ~800 tiny launches
-    per step for nothing."""
+    per step for nothing.  s3 (the fp32 eval pack): also the three-plane packs of the projections / the head for csrc/pw_s3.hip."""
     fold = _fold_bn if fold_bn else (lambda _sd, _p: (None, None))
     e = _Obj()
     e.stem_w = sd[p + "._conv_stem.weight"].permute(2, 3, 1, 0).contiguous()      # [ky][kx][ci][co]
@@ -136,10 +156,12 @@ def _pack_encoder(sd, p, dtype=torch.float32, fold_bn=True):
         b.se_w2 = sd[bp + "._se_expand.weight"].reshape(b.mid, -1).t().contiguous()      # [Cs][C]
         b.se_b2 = sd[bp + "._se_expand.bias"].contiguous()
         b.w_proj = _pack_conv(sd[bp + "._project_conv.weight"], dtype)
+        b.w_proj3 = _pack_pw_s3(b.w_proj) if s3 and b.mid >= PW_S3_MIN_MID else None
         b.s2, b.b2 = fold(sd, bp + "._bn2")
         b.skip = (s == 1 and cin == cout)                                          # model.py:126
         e.blocks.append(b)
     e.w_head = _pack_conv(sd[p + "._conv_head.weight"], dtype)
+    e.w_head3 = _pack_pw_s3(e.w_head) if s3 else None
     e.head_scale, e.head_shift = fold(sd, p + "._bn1")
     return e
 
@@ -194,6 +216,10 @@ SPLIT3 = __import__("os").environ.get("CCVPE_SPLIT3", "1") != "0"
 # pack); CCVPE_SPLIT3_TAIL=0 = exact fp32 tails (A/B runs), CCVPE_SPLIT3=0 switches it off as well
 SPLIT3_TAIL = SPLIT3 and __import__("os").environ.get("CCVPE_SPLIT3_TAIL", "1") != "0"
 SPLIT3_MIN_OK = 2          # ccvpe_upconv3x3_s3_ok value a layer needs for the route (tests open the size rule with 1)
+# ... and the fp32 1x1 GEMMs behind the encoders' depthwise stage (MBConv project from mid 240 on, _conv_head) and the two descriptor
+# heads (csrc/pw_s3.hip) where the library's size rule prefers it; CCVPE_SPLIT3_PW=0 = conv_igemm (A/B runs), CCVPE_SPLIT3=0 as well
+SPLIT3_PW = SPLIT3 and __import__("os").environ.get("CCVPE_SPLIT3_PW", "1") != "0"
+SPLIT3_PW_MIN_OK = 2       # ccvpe_pw_s3_ok value a layer needs for the route (tests open the size rule with 1)
 # train mode: replay the per-step weight re-pack as one hipGraph (see _CVMBase._packed); CCVPE_PACK_GRAPH=0 keeps it eager
 PACK_GRAPH = __import__("os").environ.get("CCVPE_PACK_GRAPH", "1") != "0"
 # train mode, fp32: the per-step re-pack as ONE gather launch (ccvpe_amd/repack.py); CCVPE_PACK_GATHER=0 keeps the graph replay
@@ -349,8 +375,9 @@ def _pack_model(sd, kind, n_tail, dtype=torch.float32, fold=True, f32_tail=0):
     pk.dtype = dtype
     pk.f32_from = 6 - f32_tail if dtype != torch.float32 else 6      # first loc level index (0..5) that runs in fp32
     base_dtype = dtype
-    pk.grd = _pack_encoder(sd, "grd_efficientnet", dtype, fold_bn=fold)
-    pk.sat = _pack_encoder(sd, "sat_efficientnet", dtype, fold_bn=fold)
+    s3 = fold and dtype == torch.float32             # the fp32 eval pack: three-plane packs beside the fp32 ones, cached with them like fw3
+    pk.grd = _pack_encoder(sd, "grd_efficientnet", dtype, fold_bn=fold, s3=s3)
+    pk.sat = _pack_encoder(sd, "sat_efficientnet", dtype, fold_bn=fold, s3=s3)
     # six ground-descriptor heads fused into one 1x1 GEMM (N = sum Cd) + height collapse
     ws, bs, wh, bh = [], [], [], []
     for l in range(1, 7):
@@ -360,6 +387,7 @@ def _pack_model(sd, kind, n_tail, dtype=torch.float32, fold=True, f32_tail=0):
         wh.append(sd[p + ".2.weight"].reshape(-1))
         bh.append(sd[p + ".2.bias"].reshape(-1))
     pk.gd_w = _pad2(torch.cat(ws, 0), dtype)
+    pk.gd_w3 = _pack_pw_s3(pk.gd_w) if s3 else None
     pk.gd_bias = torch.cat(bs, 0).contiguous()
     pk.gd_n = pk.gd_bias.shape[0]
     pk.gd_wh = torch.stack(wh, 0).contiguous()
@@ -367,6 +395,7 @@ def _pack_model(sd, kind, n_tail, dtype=torch.float32, fold=True, f32_tail=0):
     # aerial descriptor Linear(5120 -> N) == conv 2x2 stride 2 (models.py:102-104,173-184)
     w = sd["sat_feature_to_descriptors.1.weight"]
     pk.sd_w = _pack_conv(w.view(w.shape[0], 1280, 2, 2), dtype)
+    pk.sd_w3 = _pack_pw_s3(pk.sd_w) if s3 else None
     pk.sd_bias = sd["sat_feature_to_descriptors.1.bias"].contiguous()
     pk.sd_n = w.shape[0]
 
@@ -442,6 +471,20 @@ def _pack_model(sd, kind, n_tail, dtype=torch.float32, fold=True, f32_tail=0):
 # ----------------------------------------------------------------------------------------
 # forward building blocks (every line below enqueues HIP kernels through the C ABI)
 # ----------------------------------------------------------------------------------------
+def _pw(x, c0, w, w3, n, *, batch, in_h, in_w, two=False, gate=None, scale=None, shift=None, residual=None, act=ops.ACT_NONE,
+        ldd=None, out_f32=False):
+    """A 1x1 (two: 2x2 stride-2) layer: the three-plane bf16 kernel where its pack exists (eval, fp32) and the library's size rule
+    prefers it, else conv_igemm — today's call, unchanged."""
+    if (SPLIT3 and SPLIT3_PW and w3 is not None and x.dtype == torch.float32 and
+            ops.pw_s3_ok(x, c0, w3, n, batch=batch, in_h=in_h, in_w=in_w, two=two, gate=gate, residual=residual, act=act,
+                         ldd=ldd) >= SPLIT3_PW_MIN_OK):
+        return ops.pw_s3(x, c0, w3, n, batch=batch, in_h=in_h, in_w=in_w, two=two, gate=gate, scale=scale, shift=shift,
+                         residual=residual, act=act, ldd=ldd)
+    kk = dict(kh=2, kw=2, stride=2) if two else {}
+    return ops.conv_igemm(x, c0, w, n, batch=batch, in_h=in_h, in_w=in_w, gate=gate, scale=scale, shift=shift, residual=residual,
+                          act=act, ldd=ldd, out_f32=out_f32, **kk)
+
+
 def _run_encoder(e, img, circular, multiscale, dtype=torch.float32):
     """EfficientNet.extract_features[_multiscale] (efficientnet_pytorch/model.py:278-326)."""
     blk0 = e.blocks[0]
@@ -469,13 +512,13 @@ def _run_encoder(e, img, circular, multiscale, dtype=torch.float32):
             u, part = ops.dwconv(t, blk.w_dw, blk.s1, blk.b1, blk.k, blk.s, circular)
         ho, wo = u.shape[1], u.shape[2]
         gate = ops.se_gate(part, ho * wo, blk.se_w1, blk.se_b1, blk.se_w2, blk.se_b2)
-        x = ops.conv_igemm(u, blk.mid, blk.w_proj, blk.cout, batch=b, in_h=ho, in_w=wo, gate=gate,
-                           scale=blk.s2, shift=blk.b2, residual=x if blk.skip else None)
+        x = _pw(u, blk.mid, blk.w_proj, getattr(blk, "w_proj3", None), blk.cout, batch=b, in_h=ho, in_w=wo, gate=gate,
+                scale=blk.s2, shift=blk.b2, residual=x if blk.skip else None)
         if multiscale:
             feats.append(x)
     b, h, w, _ = x.shape
-    f = ops.conv_igemm(x, 320, e.w_head, 1280, batch=b, in_h=h, in_w=w, scale=e.head_scale,
-                       shift=e.head_shift, act=ops.ACT_SWISH)
+    f = _pw(x, 320, e.w_head, getattr(e, "w_head3", None), 1280, batch=b, in_h=h, in_w=w, scale=e.head_scale,
+            shift=e.head_shift, act=ops.ACT_SWISH)
     return f, feats
 
 
@@ -751,14 +794,14 @@ class _CVMBase(nn.Module):
                 if gh != spec["grd_h"]:
                     raise ValueError("ground feature height %d != %d expected by the descriptor heads"
                                      % (gh, spec["grd_h"]))
-                y1 = ops.conv_igemm(gfeat, 1280, pk.gd_w, pk.gd_n, batch=batch, in_h=gh, in_w=gw,
-                                    shift=pk.gd_bias, ldd=_round_up(pk.gd_n, 4), out_f32=True)
+                y1 = _pw(gfeat, 1280, pk.gd_w, pk.gd_w3, pk.gd_n, batch=batch, in_h=gh, in_w=gw,
+                         shift=pk.gd_bias, ldd=_round_up(pk.gd_n, 4), out_f32=True)
                 gdesc = ops.ground_descriptor(y1, pk.gd_wh, pk.gd_bh, spec["cd"])
             svol, sfeats = _run_encoder(pk.sat, sat, False, True, pk.dtype)
             main.wait_stream(side)
             gdesc.record_stream(main)
-            sdesc = ops.conv_igemm(svol, 1280, pk.sd_w, pk.sd_n, batch=batch, in_h=svol.shape[1],
-                                   in_w=svol.shape[2], kh=2, kw=2, stride=2, shift=pk.sd_bias)
+            sdesc = _pw(svol, 1280, pk.sd_w, pk.sd_w3, pk.sd_n, batch=batch, in_h=svol.shape[1],
+                        in_w=svol.shape[2], two=True, shift=pk.sd_bias)
 
             overlap = _overlap_decoders(self.precision, batch)
             loc_shifts = self._loc_shifts()

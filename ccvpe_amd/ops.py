@@ -394,6 +394,74 @@ def upconv3x3_s3(src0, c0, w3_packed, shift9, n, *, batch, h1, w1, src1=None, c1
     return dst
 
 
+def _pw_s3_desc(src0, c0, w3_packed, n, batch, in_h, in_w, two, gate, scale, shift, residual, act, dst, ldd, ld0):
+    d = ConvDesc()
+    d.src0, d.src1, d.gate, d.w = _ptr(src0), None, _ptr(gate), _ptr(w3_packed)
+    d.scale, d.shift, d.residual = _ptr(scale), _ptr(shift), _ptr(residual)
+    d.dst = _ptr(dst) if dst is not None else None
+    d.c0, d.ld0, d.c1, d.ld1 = c0, ld0, 0, 0
+    d.batch, d.in_h, d.in_w = batch, in_h, in_w
+    d.kh, d.kw, d.stride, d.pad = (2, 2, 2, 0) if two else (1, 1, 1, 0)
+    d.n, d.kpad = n, w3_packed.shape[0] * w3_packed.shape[2]
+    d.ldd = ldd
+    d.ldres = residual.shape[-1] if residual is not None else 0
+    d.act, d.out_mode = act, OUT_NHWC
+    return d
+
+
+def pw_s3_ok(src0, c0, w3_packed, n, *, batch, in_h, in_w, two=False, gate=None, residual=None, act=ACT_NONE, ldd=None, ld0=None):
+    """ccvpe_pw_s3_ok for this 1x1 (two: 2x2 stride-2) layer: 0 = not served (also: anything but fp32 tensors, no three-plane pack
+    or one whose rows are not round_up(n, 16)), 1 = the kernel computes it, 2 = and the library's measured size rule prefers it to
+    conv_igemm.  Nothing is launched."""
+    if w3_packed is None or src0.dtype != torch.float32 or (residual is not None and residual.dtype != torch.float32):
+        return 0
+    if w3_packed.dtype != torch.bfloat16 or w3_packed.dim() != 3 or w3_packed.shape[1] != (n + 15) // 16 * 16 or w3_packed.shape[2] != 48:
+        return 0
+    ld0 = ld0 if ld0 is not None else src0.shape[-1]
+    d = _pw_s3_desc(src0, c0, w3_packed, n, batch, in_h, in_w, two, gate, None, None, residual, act, None, ldd if ldd is not None else n, ld0)
+    return int(_lib.load().ccvpe_pw_s3_ok(ctypes.byref(d)))
+
+
+def pw_s3_route_name(desc):
+    """Kernel name of ccvpe_pw_s3_f32(desc) as rocprofv3 prints it (minus namespace): ccvpe_pw_s3_route, no launch."""
+    r = _lib.load().ccvpe_pw_s3_route(ctypes.byref(desc))
+    if r <= 0:
+        raise _lib.CcvpeError("ccvpe_pw_s3_route: the kernel does not compute this layer")
+    return "pw_s3_kernel<%d,%d,%d,%d>" % ((r >> 8) & 0xf, (r >> 12) & 0xf, (r >> 16) & 0xf, (r >> 20) & 0xf)
+
+
+def pw_s3(src0, c0, w3_packed, n, *, batch, in_h, in_w, two=False, gate=None, scale=None, shift=None, residual=None, act=ACT_NONE,
+          dst=None, ldd=None, ld0=None):
+    """conv_igemm's fp32 1x1 layer (two: the 2x2 stride-2 layer) with its products on the bf16 matrix cores, three bf16 planes per
+    fp32 operand (ccvpe_pw_s3_f32); w3_packed from models._pack_pw_s3.  Same result as conv_igemm to fp32 rounding, not bit for bit.
+    fp32 tensors only; a layer the kernel does not serve is an error (no fallback)."""
+    lib = _lib.load()
+    for t, nm in ((src0, "src0"), (gate, "gate"), (scale, "scale"), (shift, "shift"), (residual, "residual"), (dst, "dst")):
+        _chk(t, nm)
+    _chk(w3_packed, "w", torch.bfloat16)
+    if w3_packed.dim() != 3 or w3_packed.shape[1] != (n + 15) // 16 * 16 or w3_packed.shape[2] != 48:
+        raise ValueError("w is not the three-plane pack of models._pack_pw_s3 for n = %d" % n)
+    ld0 = ld0 if ld0 is not None else src0.shape[-1]
+    ho, wo = (in_h // 2, in_w // 2) if two else (in_h, in_w)
+    if dst is None:
+        ldd = ldd if ldd is not None else n
+        dst = _empty((batch, ho, wo, ldd), device=src0.device)
+    elif ldd is None:
+        ldd = dst.shape[-1]
+    d = _pw_s3_desc(src0, c0, w3_packed, n, batch, in_h, in_w, two, gate, scale, shift, residual, act, dst, ldd, ld0)
+    rec = _recorder
+    ev0 = rec.begin() if rec is not None else None
+    check(lib.ccvpe_pw_s3_f32(ctypes.byref(d), _stream()), "ccvpe_pw_s3_f32")
+    if rec is not None:
+        # the fp32 layer's FLOPs and bytes (as conv_igemm): this kernel's "TF" in the bench tables can exceed the fp32 peak
+        m = batch * ho * wo
+        k_alg = (4 if two else 1) * c0
+        flops = 2.0 * m * n * k_alg
+        nbytes = 4.0 * (batch * in_h * in_w * c0 + m * n + n * k_alg + (m * n if residual is not None else 0))
+        rec.end(pw_s3_route_name(d), "%s M%d N%d K%d" % ("2x2 s2" if two else "1x1 s1", m, n, k_alg), flops, nbytes, ev0)
+    return dst
+
+
 def tail512(x, c0, w_packed, shift9, w2, b2, cout, normalize, *, batch, h1, w1, split=False, want_softmax=False):
     """The whole 512 x 512 decoder level in one launch (ccvpe_tail512_f32 / _bf16): folded deconv + conv.0 + ReLU + conv.2
     (+ F.normalize for cout = 2).  x [B,h1,w1,ld0]; w_packed / shift9 from models._pack_upconv (n = 16, no skip);

@@ -205,6 +205,21 @@ int ccvpe_upconv3x3_s3_form_ok(const ccvpe_upconv_desc* desc, int form);
 int ccvpe_upconv3x3_s3_route(const ccvpe_upconv_desc* desc, int form);
 int ccvpe_upconv3x3_s3_form_f32(const ccvpe_upconv_desc* desc, int form, void* stream);
 int ccvpe_set_s3_quad(int on);
+/* (ABI 7, additive) The fp32 1x1 GEMMs behind the encoders' depthwise stage (MBConv project with the SE gate on its input, the
+ * 320 -> 1280 head) and the two descriptor heads in the same three-plane arithmetic (csrc/pw_s3.hip): fp32-class error, not
+ * bit-identical to ccvpe_conv_igemm_f32, bit-identical run to run (one pass, no K split).  desc as for ccvpe_conv_igemm_f32 —
+ * fp32 tensors, one source, NHWC store, act none or swish, gate / scale / shift / residual as there — for (kh, kw, stride, pad) =
+ * (1, 1, 1, 0) or (2, 2, 2, 0), c0 % 16 == 0, n > 48, except `w` / `kpad`: the three-plane pack [K / 16][npad16][hi 16 | mid 16 | lo 16]
+ * bf16 (models._pack_pw_s3; k = (ky * 2 + kx) * c0 + channel as in the fp32 pack, stage = k / 16), kpad = 3 * K.
+ * ccvpe_pw_s3_ok launches nothing: 0 = not served (any other layer, bf16 storage is the caller's to exclude, K % 16 != 0, a kpad
+ * that is not this pack's, misaligned pointers), 1 = computed correctly, 2 = and the measured size rule prefers it to
+ * ccvpe_conv_igemm_f32 (with its split-K second pass where it has one).  ccvpe_pw_s3_route launches nothing: 0 where _ok is 0, else
+ * 1 | MT << 8 | NT << 12 | WN << 16 | NW << 20 of pw_s3_kernel<MT, NT, WN, NW> (NW waves; workgroup tile = 16*MT*(NW/WN) rows x
+ * 16*NT*WN columns), for the launch recorder's names.  ccvpe_pw_s3_f32 runs every desc with _ok >= 1 and returns CCVPE_EINVAL otherwise.  What
+ * ccvpe_conv_igemm_* route is unchanged. */
+int ccvpe_pw_s3_ok(const ccvpe_conv_desc* desc);
+int ccvpe_pw_s3_route(const ccvpe_conv_desc* desc);
+int ccvpe_pw_s3_f32(const ccvpe_conv_desc* desc, void* stream);
 
 /* -------------------------------------------------------------------------------------------
  * The whole 512 x 512 level of a decoder in one launch (csrc/tail512.hip):
