@@ -190,6 +190,8 @@ PROTOTYPES = {
                                                 c_void_p, c_void_p, c_int, ctypes.POINTER(c_float), ctypes.POINTER(c_float),
                                                 c_void_p, c_int, c_int, c_void_p]),
     "ccvpe_kitti_align_u8": (c_int, [c_void_p, ctypes.c_long, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p]),
+    "ccvpe_kitti_align_norm_u8_f32": (c_int, [c_void_p, c_void_p, c_int, ctypes.POINTER(c_float), ctypes.POINTER(c_float),
+                                              c_void_p, c_int, c_int, c_void_p]),
     "ccvpe_conv_igemm_bf16": (c_int, [ctypes.POINTER(ConvDesc), c_int, c_void_p]),
     "ccvpe_stem_conv_bf16": (c_int, [c_void_p] * 5 + [c_int] * 4 + [c_void_p]),
     "ccvpe_dwconv_bf16": (c_int, [c_void_p] * 6 + [c_int] * 7 + [c_void_p]),

@@ -11,7 +11,9 @@ The reference aligns every aerial map on the host with four Pillow passes over t
 
 This module is the written specification of `ccvpe_kitti_align_u8` (csrc/align.hip), which evaluates the chain LAZILY for
 the crop window only.  Nothing here imports PIL; tests/test_kitti_align.py runs Pillow itself as the reference and asks
-for equal bytes.
+for equal bytes.  `ccvpe_kitti_align_norm_u8_f32` is the same chain over a table of device addresses (maps resident in the device
+image cache) that writes the normalised fp32 NCHW batch side itself; `align_norm_spec` is its specification, `kitti_align_norm`
+its launch (tests/test_kitti_map_cache*.py).
 
 Pillow's arithmetic (Pillow 12.2: PIL/Image.py `rotate`, src/libImaging/Geometry.c `affine_fixed`, `affine_transform`,
 `bilinear_filter32RGB`):
@@ -34,6 +36,8 @@ A parameter row (`kitti_align_params`) is ROW_LEN int64 values:
 import math
 
 import numpy as np
+
+from .preprocess import IMAGENET_MEAN, IMAGENET_STD
 
 ROW_LEN = 20
 _IDENT = (65536, 0, 32768, 0, 65536, 32768)
@@ -179,7 +183,20 @@ def align_reference(src_u8, row, crop=512):
     return np.where(in_image, nearest_at(p3, w, h, r2, x, y), np.uint8(0))
 
 
-# ---- the device launch -----------------------------------------------------------------------------------------------------
+def align_norm_spec(src_list, rows, crop, mean=IMAGENET_MEAN, std=IMAGENET_STD):
+    """What ccvpe_kitti_align_norm_u8_f32 computes, in numpy: src_list = B arrays [h, w, 3] uint8 (repeats allowed; None = the
+    all-zero crop of a row whose address is 0), rows [B, ROW_LEN], crop = side or (crop_h, crop_w).  `align_reference` per
+    sample, then the fp32 ToTensor / Normalize of cache.gather_spec with roll 0.  Returns [B, 3, crop_h, crop_w] float32."""
+    from .cache import gather_spec
+    crop_h, crop_w = (crop, crop) if np.isscalar(crop) else crop
+    crops = [np.zeros((crop_h, crop_w, 3), dtype=np.uint8) if src is None else align_reference(src, row, (crop_h, crop_w))
+             for src, row in zip(src_list, rows)]
+    if not crops:
+        return np.empty((0, 3, crop_h, crop_w), dtype=np.float32)
+    return gather_spec(crops, [0] * len(crops), mean=mean, std=std)
+
+
+# ---- the device launches ---------------------------------------------------------------------------------------------------
 def kitti_align(src_u8, offsets, rows, crop_hw, out=None):
     """ONE launch for a batch: src_u8 = packed uint8 device buffer of decoded [h, w, 3] maps, offsets int64 [B] (device) =
     each sample's first byte in it, rows int64 [B, ROW_LEN] (device).  Returns / writes out [B, crop_h, crop_w, 3] uint8.
@@ -201,3 +218,32 @@ def kitti_align(src_u8, offsets, rows, crop_hw, out=None):
     _lib.check(lib.ccvpe_kitti_align_u8(src_u8.data_ptr(), src_u8.numel(), offsets.data_ptr(), rows.data_ptr(), b,
                                         out.data_ptr(), crop_h, crop_w, ops._stream()), "ccvpe_kitti_align_u8")
     return out
+
+
+def kitti_align_norm(srcs, rows, crop_hw, dst=None, mean=IMAGENET_MEAN, std=IMAGENET_STD):
+    """ONE launch for a batch side, from maps that already lie on the device: srcs int64 [B] (device) = the device address of
+    each sample's decoded [h, w, 3] uint8 map (raw slots of the device image cache, or any live uint8 device memory of that
+    size; repeats allowed; 0 = an all-zero crop, never read), rows int64 [B, ROW_LEN] (device).  Writes / returns
+    dst [B, 3, crop_h, crop_w] fp32: the aligned crop through ToTensor -> Normalize, bit-identical to `kitti_align` followed by
+    `preprocess.gather_norm`, with no uint8 crop in between.  The caller keeps the addressed memory alive."""
+    import ctypes
+
+    import torch
+    from . import _lib, ops
+    lib = _lib.load()
+    for t, nm in ((srcs, "srcs"), (rows, "rows")):
+        if not (t.is_cuda and t.dtype == torch.int64 and t.is_contiguous()):
+            raise ValueError("%s must be a contiguous int64 device tensor (no CPU fallback)" % nm)
+    b = int(rows.shape[0])
+    if rows.dim() != 2 or rows.shape[1] != ROW_LEN or tuple(srcs.shape) != (b,) or srcs.device != rows.device:
+        raise ValueError("rows must be [B,%d] and srcs [B], on one device" % ROW_LEN)
+    crop_h, crop_w = crop_hw
+    if dst is None:
+        dst = torch.empty((b, 3, crop_h, crop_w), device=rows.device, dtype=torch.float32)
+    if not (dst.is_cuda and dst.dtype == torch.float32 and dst.is_contiguous() and tuple(dst.shape) == (b, 3, crop_h, crop_w)):
+        raise ValueError("dst must be a contiguous [%d,3,%d,%d] fp32 device tensor" % (b, crop_h, crop_w))
+    m = (ctypes.c_float * 3)(*mean)
+    s = (ctypes.c_float * 3)(*std)
+    _lib.check(lib.ccvpe_kitti_align_norm_u8_f32(srcs.data_ptr(), rows.data_ptr(), b, m, s, dst.data_ptr(), crop_h, crop_w,
+                                                 ops._stream()), "ccvpe_kitti_align_norm_u8_f32")
+    return dst

@@ -12,10 +12,15 @@ is NO eviction: when no slot is left, `full` turns true and new images are simpl
 slots and the same gather launch).  The host table is guarded by a lock: lookups come from DeviceBatches' producer thread,
 inserts from the consumer thread.  `device="cpu"` keeps the same books over CPU tensors and launches nothing (tests).
 
+RAW slots (`insert_raw`): the decoded image as it is, for sources a kernel reads whole — KITTI's 1280 x 1280 aerial maps
+(4.9 MB each), which ccvpe_kitti_align_norm_u8_f32 aligns and normalises from a table of slot addresses
+(KITTIPairs(device_align=True, cache_maps=True); ccvpe_amd.align.kitti_align_norm).  Same chunks per shape, capacity, lock,
+counters and `full` rule; `raw_key` keeps a file's raw entry apart from its resized ones.
+
 `gather_spec` is the numpy fp32 specification of the gather kernel.
 
-Not done here: KITTI's 1280 x 1280 source maps for the align kernel, a device-resident Oxford map for
-training patches, eviction policies, pinned staging for the first epoch's uploads."""
+Not done here: caching only the window of a KITTI map the alignment can reach, eviction policies, pinned
+staging for the first epoch's uploads."""
 import threading
 
 import numpy as np
@@ -53,7 +58,8 @@ class _Shape(object):
 
 
 class DeviceImageCache(object):
-    """key (str) -> (device address, resized (h, w), raw (h, w)) of a resized uint8 image in `device` memory.
+    """key (str) -> (device address, resized (h, w), raw (h, w)) of a resized uint8 image in `device` memory (a raw entry:
+    both sizes are the image's own).
 
     capacity_bytes bounds the chunks' total size; chunk_bytes is the allocation granule (a chunk holds
     max(1, chunk_bytes // (h * w * 3)) slots, fewer when less capacity is left — a chunk belongs to ONE shape, so keep
@@ -139,6 +145,36 @@ class DeviceImageCache(object):
             self._table[key] = (slot.data_ptr(), out_hw, raw_hw)
             self.entries += 1
             self.bytes_used += out_hw[0] * out_hw[1] * 3
+        return slot.data_ptr()
+
+    @staticmethod
+    def raw_key(key):
+        """The key under which `insert_raw` callers keep the UNRESIZED image of source file `key`: resized entries are keyed
+        "<file>|<h>x<w>" (DeviceBatches), so a raw entry and a resized entry of one file never collide."""
+        return "%s|raw" % key
+
+    def insert_raw(self, key, img_u8):
+        """Retain the decoded [h, w, 3] uint8 image AS IT IS (KITTI's aerial maps: the align kernel reads the whole map) in a
+        free slot of its own shape and remember it under `key`; chunks per (h, w), capacity, lock, counters and the `full`
+        rule are those of `insert`.  img_u8: a tensor on `device` (a view of the batch's staged upload, say), copied into the
+        slot on the current stream.  Returns the slot's address; the address already stored when `key` is present (a no-op:
+        nothing is copied); None when the cache is full (the image is not retained).  `lookup` returns the raw (h, w)."""
+        if len(img_u8.shape) != 3 or img_u8.shape[2] != 3 or min(img_u8.shape) <= 0:
+            raise ValueError("img_u8 must be [h,w,3] uint8")
+        hw = (int(img_u8.shape[0]), int(img_u8.shape[1]))
+        with self._lock:
+            e = self._table.get(key)
+            if e is not None:
+                return e[0]
+            slot = self._slot(hw)
+            if slot is None:
+                return None
+        if self.device.type != "cpu":                       # stream-ordered: the align launch that reads the slot comes later
+            slot.copy_(img_u8, non_blocking=True)
+        with self._lock:                                    # published only now: a lookup never sees a slot nobody has filled
+            self._table[key] = (slot.data_ptr(), hw, hw)
+            self.entries += 1
+            self.bytes_used += hw[0] * hw[1] * 3
         return slot.data_ptr()
 
     def scratch(self, batch, out_hw):

@@ -18,7 +18,9 @@ KITTI (datasets.py:354-640, train_KITTI.py:46-100): `KITTIPairs(root, file, ...)
 the two images of a sample and performs the aerial image's geometric alignment — rotate to the vehicle heading, shift to the
 camera, the random (training) or listed (test files) shift and rotation, centre crop — with the same PIL calls as the reference
 (the result is the 512 x 512 uint8 crop), or, with `device_align=True`, leaves the alignment to ONE ccvpe_kitti_align_u8 launch per
-batch that DeviceBatches makes on the decoded maps (ccvpe_amd/align.py, csrc/align.hip: bit-identical to the PIL calls).  Resize + normalise of both images
+batch that DeviceBatches makes on the decoded maps (ccvpe_amd/align.py, csrc/align.hip: bit-identical to the PIL calls); with
+`cache_maps=True` and a device image cache the decoded maps stay in HBM and ONE ccvpe_kitti_align_norm_u8_f32 launch per batch aligns
+and normalises them from a table of addresses, so an epoch after the first opens no image.  Resize + normalise of both images
 and the 1 + 16 + 2 channel ground truth then run on the device exactly as for VIGOR:
 
     pairs = KITTIPairs(root, "train_files.txt", shift_range_lat=20, shift_range_lon=20, rotation_range=10)
@@ -195,11 +197,18 @@ class KITTIPairs(object):
 
     device_align=True leaves the alignment to the device: sample() returns the map AS DECODED (`sat_src_u8`) and the parameter row
     of ccvpe_amd/align.py (`align`) instead of `sat_u8`; DeviceBatches then aligns the whole batch with one launch of
-    ccvpe_kitti_align_u8, bit-identical to the Pillow calls.  Every other key, and every draw, is the same."""
+    ccvpe_kitti_align_u8, bit-identical to the Pillow calls.  Every other key, and every draw, is the same.
+
+    cache_maps=True (with device_align=True; opt-in): the decoded map of a sample never changes between epochs, only its draw
+    does, so `keys` also names the map file ("sat_src") and DeviceBatches with a cache keeps the decoded map on the device;
+    sample(cached={"sat_src": (h, w)}) then does not open the map and builds the same `align` row from the cached size."""
 
     def __init__(self, root, file, shift_range_lat=20.0, shift_range_lon=20.0, rotation_range=10.0, test=False, rng=None,
-                 device_align=False):
+                 device_align=False, cache_maps=False):
         self.root, self.test, self.device_align = root, bool(test), bool(device_align)
+        self.cache_maps = bool(cache_maps)
+        if self.cache_maps and not self.device_align:
+            raise ValueError("cache_maps=True needs device_align=True: the cached maps are aligned on the device")
         self.meter_per_pixel = kitti_meter_per_pixel()
         self.shift_px_lat = shift_range_lat / self.meter_per_pixel
         self.shift_px_lon = shift_range_lon / self.meter_per_pixel
@@ -236,21 +245,32 @@ class KITTIPairs(object):
 
     def keys(self, idx, draws):
         """Source files of sample idx for a device image cache: the camera image; the aerial side is None — the aligned crop
-        depends on the sample's draw (both device_align modes keep their path)."""
+        depends on the sample's draw (both device_align modes keep their path).  cache_maps: "sat_src" names the map file,
+        whose DECODED image does not depend on the draw."""
         name = self.lines[idx].split(" ")[0] if self.test else self.lines[idx]
-        return {"grd": self.paths(name)[2], "sat": None}
+        sat_path, _, grd_path = self.paths(name)
+        if self.cache_maps:
+            return {"grd": grd_path, "sat": None, "sat_src": sat_path}
+        return {"grd": grd_path, "sat": None}
 
     def sample(self, idx, sat_hw=(512, 512), grd_hw=(256, 1024), draws=None, cached=None):
         """Decode + align sample idx.  Returns the dict DeviceBatches consumes: grd_u8 (the left camera image as decoded),
         sat_u8 (the aligned, perturbed 512 x 512 aerial crop; device_align: sat_src_u8 and align in its place), roll = 0, angle_deg
         (orientation ground truth in [0, 360]),
         center = (x_offset, y_offset) of the Gaussian (datasets.py:475-476), city = the drive, index.
-        cached: {"grd": raw (h, w)} when a device image cache holds the camera image — it is then not opened, grd_u8 is None."""
+        cached: {"grd": raw (h, w)} when a device image cache holds the camera image — it is then not opened, grd_u8 is None;
+        {"sat_src": (h, w)} (cache_maps) when it holds the decoded map — the map is not opened, sat_src_u8 is None and the
+        `align` row is built from that size."""
         from PIL import Image
         name = self.lines[idx].split(" ")[0] if self.test else self.lines[idx]
         sat_path, oxts_path, grd_path = self.paths(name)
-        with Image.open(sat_path, "r") as im:
-            sat = im.convert("RGB")
+        if self.cache_maps and cached is not None and "sat_src" in cached:
+            sat = None
+            h, w = (int(v) for v in cached["sat_src"])
+        else:
+            with Image.open(sat_path, "r") as im:
+                sat = im.convert("RGB")
+            w, h = sat.size
         with open(oxts_path) as f:
             heading = float(f.readline().split(" ")[5])
         if cached is not None and "grd" in cached:
@@ -260,14 +280,13 @@ class KITTIPairs(object):
                 grd = np.array(im.convert("RGB"))
         sx, sy, ori = self.perturbation(idx) if draws is None else draws
         mpp = self.meter_per_pixel
-        w, h = sat.size
         if w < KITTI_CROP or h < KITTI_CROP:
             raise ValueError("%s: aerial map %dx%d is smaller than the %d crop" % (sat_path, w, h, KITTI_CROP))
         cam_px = (KITTI_CAMERA_SHIFT[0] / mpp, KITTI_CAMERA_SHIFT[1] / mpp)
         shift_px = (sx * self.shift_px_lon, -sy * self.shift_px_lat)
         if self.device_align:
             from . import align
-            aerial = dict(sat_src_u8=np.array(sat),
+            aerial = dict(sat_src_u8=None if sat is None else np.array(sat),
                           align=align.kitti_align_params(heading, cam_px, shift_px, ori, w, h, KITTI_CROP))
         else:
             sat = sat.rotate(-heading / np.pi * 180)                                # east = the vehicle heading
@@ -492,6 +511,12 @@ class DeviceBatches(object):
     the misses of a full cache go through the cache's scratch slots and the same launch.  Draws are made in the same order and
     the batches are bit-identical to those without a cache.
 
+    KITTIPairs(device_align=True, cache_maps=True) with a cache: the DECODED aerial maps stay on the device too (raw slots).  The
+    producer looks the map keys up and decodes only the misses; the consumer stages and uploads only those (one pinned buffer),
+    retains each new file once, reads what a full cache cannot retain from the staged upload itself, and makes ONE
+    ccvpe_kitti_align_norm_u8_f32 launch over the address table straight into batch.sat (sat_hw must be (512, 512)); the ground
+    side goes through the gather as before.  Bit-identical to device_align=True without the flag, draws in the same order.
+
     OxfordPairs(device_map=True): the aerial side of every batch, with or without a cache, is ONE
     ccvpe_window_resize_norm_u8_f32 launch on the index's device-resident map over a [B, 2] table of patch origins, written
     straight into batch.sat (tables from `sat_hw`); it never touches the cache.  Bit-identical to device_map=False."""
@@ -516,6 +541,10 @@ class DeviceBatches(object):
         self.keep_w = int(grd_hw[1] * fov / 360)                              # train_VIGOR.py:177: int(w * FoV / 360)
         self.targets, self.n_bins, self.drop_last, self.ascending_bins = targets, n_bins, drop_last, bool(ascending_bins)
         self._stage, self._stage_free = None, None          # device alignment: the pinned staging buffer and its upload's event
+        # KITTIPairs(cache_maps=True) with a cache: decoded maps stay on the device, the align launch writes batch.sat itself
+        self._maps = cache is not None and bool(getattr(pairs, "cache_maps", False))
+        if self._maps and self.sat_hw != (KITTI_CROP, KITTI_CROP):
+            raise ValueError("cache_maps: the align launch writes the model's input, sat_hw must be (%d, %d)" % (KITTI_CROP, KITTI_CROP))
 
     def __len__(self):
         n = len(self.indices)
@@ -538,10 +567,12 @@ class DeviceBatches(object):
         cache keys (`_keys`) and the slot addresses found (`_addr`) to the consumer."""
         keys, found = [], []
         for i, d in zip(chunk, draws):
-            k = self.pairs.keys(int(i), d)
-            k = {side: None if k[side] is None else self._cache_key(side, k[side]) for side in ("grd", "sat")}
+            named = self.pairs.keys(int(i), d)
+            k = {side: None if named[side] is None else self._cache_key(side, named[side]) for side in ("grd", "sat")}
+            if self._maps:                                   # the decoded map, unresized: a key of its own kind
+                k["sat_src"] = self.cache.raw_key(named["sat_src"])
             keys.append(k)
-            hits = {side: self.cache.lookup(k[side]) for side in ("grd", "sat") if k[side] is not None}
+            hits = {side: self.cache.lookup(key) for side, key in k.items() if key is not None}
             found.append({side: hit for side, hit in hits.items() if hit is not None})
 
         def one(a):
@@ -593,7 +624,14 @@ class DeviceBatches(object):
         """KITTIPairs(device_align=True): the batch's decoded maps packed into ONE pinned staging buffer (reused across batches),
         one upload, the parameter rows, one ccvpe_kitti_align_u8 launch -> [B, 512, 512, 3] uint8 crops on the device."""
         from . import align
-        sizes = [s["sat_src_u8"].size for s in samples]
+        src, offsets = self._upload_packed([s["sat_src_u8"] for s in samples])
+        rows = torch.from_numpy(np.stack([s["align"] for s in samples])).to(self.device)
+        return align.kitti_align(src, torch.from_numpy(offsets[:-1].copy()).to(self.device), rows, (KITTI_CROP, KITTI_CROP))
+
+    def _upload_packed(self, maps):
+        """The decoded maps back to back in the pinned staging buffer (reused across batches), ONE upload.  Returns the device
+        buffer and the int64 offsets [len(maps) + 1] of the maps in it."""
+        sizes = [m.size for m in maps]
         offsets = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
         total = int(offsets[-1])
         if self._stage is None or self._stage.numel() < total:
@@ -601,13 +639,42 @@ class DeviceBatches(object):
         elif self._stage_free is not None:
             self._stage_free.synchronize()                   # the previous batch's upload has read the buffer
         stage = self._stage.numpy()
-        for s, o, n in zip(samples, offsets, sizes):
-            stage[o:o + n] = s["sat_src_u8"].reshape(-1)
+        for m, o, n in zip(maps, offsets, sizes):
+            stage[o:o + n] = m.reshape(-1)
         src = self._stage[:total].to(self.device, non_blocking=True)
         self._stage_free = torch.cuda.Event()
         self._stage_free.record()
+        return src, offsets
+
+    def _align_cached_maps(self, samples, dst):
+        """KITTIPairs(device_align=True, cache_maps=True) with a cache: the aerial side of a batch from device-resident maps.
+        Only the maps the producer had to decode are staged and uploaded (each file once); each new key is retained in a raw
+        slot of the cache, a map that cannot be retained (cache full) is read from the staged upload itself; then the address
+        table and ONE ccvpe_kitti_align_norm_u8_f32 launch straight into dst = batch.sat."""
+        from . import align
+        cache = self.cache
+        addrs, pending, first = [], [], {}
+        for s in samples:
+            key = s["_keys"]["sat_src"]
+            addr = s["_addr"].get("sat_src")
+            if addr is None:                                 # inserted by a batch that was still in flight when the producer
+                addr = cache.address(key)                    # looked the key up
+            if addr is None and key not in first:            # an earlier sample of this batch stages the same file
+                first[key] = len(pending)
+                pending.append(s["sat_src_u8"])
+            addrs.append(addr)
+        if pending:
+            src, offsets = self._upload_packed(pending)
+            staged = {}
+            for key, j in first.items():
+                h, w = pending[j].shape[:2]
+                view = src[int(offsets[j]):int(offsets[j + 1])].view(h, w, 3)
+                addr = cache.insert_raw(key, view)
+                staged[key] = view.data_ptr() if addr is None else addr
+            addrs = [staged[s["_keys"]["sat_src"]] if a is None else a for a, s in zip(addrs, samples)]
+        table = torch.tensor(addrs, dtype=torch.int64, device=self.device)
         rows = torch.from_numpy(np.stack([s["align"] for s in samples])).to(self.device)
-        return align.kitti_align(src, torch.from_numpy(offsets[:-1].copy()).to(self.device), rows, (KITTI_CROP, KITTI_CROP))
+        align.kitti_align_norm(table, rows, (KITTI_CROP, KITTI_CROP), dst=dst)   # `src` lives until here: stream-ordered free
 
     def _window_side(self, samples, dst):
         """OxfordPairs(device_map=True): the aerial side of a batch = the origins table + ONE launch on the resident map."""
@@ -622,11 +689,14 @@ class DeviceBatches(object):
         out = Batch()
         out.grd = torch.empty((b, 3, self.grd_hw[0], self.keep_w), device=dev, dtype=torch.float32)
         out.sat = torch.empty((b, 3) + self.sat_hw, device=dev, dtype=torch.float32)
-        crops = self._align_on_device(samples) if b and "align" in samples[0] else None
+        maps = bool(b) and self._maps                         # the aerial side is aligned from device-resident maps
+        crops = self._align_on_device(samples) if b and "align" in samples[0] and not maps else None
         window = bool(b) and "sat_origin" in samples[0]       # the aerial side comes from a device-resident map
         if self.cache is not None:
             self._gather_side(samples, "grd", self.grd_hw, self.keep_w, out.grd)
-            if not window:
+            if maps:
+                self._align_cached_maps(samples, out.sat)
+            elif not window:
                 self._gather_side(samples, "sat", self.sat_hw, self.sat_hw[1], out.sat, crops=crops)
         else:
             for i, s in enumerate(samples):

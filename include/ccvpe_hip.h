@@ -753,6 +753,21 @@ int ccvpe_kitti_align_u8(const unsigned char* src, long src_bytes, const long lo
                          int batch, unsigned char* dst, int crop_h, int crop_w, void* stream);
 
 /* -------------------------------------------------------------------------------------------
+ * KITTI aerial alignment from device-resident maps, straight into the model's input (csrc/align.hip; ccvpe_amd/cache.py
+ * raw slots): the same lazy chain, ONE launch per batch side, no uint8 crop in memory.
+ *   srcs [batch] int64 (device) = DEVICE ADDRESSES of the decoded [h][w][3] uint8 maps (a pointer table: the maps may lie
+ *   in any number of allocations, several rows may name the same address); rows [batch][20] int64 as above, w and h of
+ *   each map from its row; dst [batch][3][crop_h][crop_w] fp32,
+ *   dst[b][c][y][x] = ((float)byte / 255 - mean[c]) / std[c], byte = what ccvpe_kitti_align_u8 writes for that pixel, the
+ *   fp32 arithmetic that of ccvpe_gather_norm_u8_f32 (bit-identical to align + gather).  mean / std: HOST pointers to 3 floats.
+ *   A row whose address is 0, or whose w or h is outside 1..32767, is an all-zero crop and is never dereferenced; every
+ *   other address must be readable for w * h * 3 bytes (the caller keeps the memory alive).
+ *   batch == 0 succeeds without a launch (tables may be null); batch <= 65535 (grid z).
+ * ----------------------------------------------------------------------------------------- */
+int ccvpe_kitti_align_norm_u8_f32(const long long* srcs, const long long* rows, int batch, const float* mean,
+                                  const float* stdv, float* dst, int crop_h, int crop_w, void* stream);
+
+/* -------------------------------------------------------------------------------------------
  * bf16 storage variants (BASELINE configs C2 / C4).  Same kernels instantiated for bf16 NHWC
  * activations and bf16 packed weights (kpad a multiple of 32), fp32 accumulation on
  * v_mfma_f32_16x16x32_bf16, fp32 scale/shift/gate/bias, round-to-nearest-even on store.  Pointers
