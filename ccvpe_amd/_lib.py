@@ -111,6 +111,8 @@ PROTOTYPES = {
     "ccvpe_stem_dw_f32": (c_int, [c_void_p] * 9 + [c_int] * 4 + [c_void_p]),
     "ccvpe_stem_dw_bf16": (c_int, [c_void_p] * 9 + [c_int] * 4 + [c_void_p]),
     "ccvpe_mbconv_front_f32": (c_int, [c_void_p, c_void_p, c_int] + [c_void_p] * 7 + [c_int] * 8 + [c_void_p]),
+    "ccvpe_mbconv_front_s3_ok": (c_int, [c_int] * 7),
+    "ccvpe_mbconv_front_s3_f32": (c_int, [c_void_p, c_void_p, c_int] + [c_void_p] * 7 + [c_int] * 8 + [c_void_p]),
     "ccvpe_se_gate_f32": (c_int, [c_void_p, c_int, c_float] + [c_void_p] * 5 + [c_int] * 3 + [c_void_p]),
     "ccvpe_ground_descriptor_f32": (c_int, [c_void_p, c_int, c_void_p, c_void_p, ctypes.POINTER(c_int),
                                             c_void_p, c_int, c_int, c_int, c_void_p]),

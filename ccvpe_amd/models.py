@@ -134,9 +134,13 @@ def _unpack_pw_s3(w3):
 PW_S3_MIN_MID = 240
 
 
+MB_S3_MAX_CIN = 48         # the fused early-block kernel's widest input (csrc/mbconv_front.hip: MBF_MAX_KK pieces of 16 channels)
+
+
 def _pack_encoder(sd, p, dtype=torch.float32, fold_bn=True, s3=False):
     """fold_bn=False (train mode): BatchNorm uses batch statistics, the folded scale/shift would be ~800 tiny launches
-    per step for nothing.  s3 (the fp32 eval pack): also the three-plane packs of the projections / the head for csrc/pw_s3.hip."""
+    per step for nothing.  s3 (the fp32 eval pack): also the three-plane packs of the projections / the head for csrc/pw_s3.hip and
+    of the early blocks' expand weights for the three-plane front kernel."""
     fold = _fold_bn if fold_bn else (lambda _sd, _p: (None, None))
     e = _Obj()
     e.stem_w = sd[p + "._conv_stem.weight"].permute(2, 3, 1, 0).contiguous()      # [ky][kx][ci][co]
@@ -149,6 +153,8 @@ def _pack_encoder(sd, p, dtype=torch.float32, fold_bn=True, s3=False):
         if b.expand:
             b.w_exp = _pack_conv(sd[bp + "._expand_conv.weight"], dtype)
             b.s0, b.b0 = fold(sd, bp + "._bn0")
+            # early blocks (the fused front kernel's, Cin <= 48): the three-plane pack of the expand weights for mbconv_front_s3_kernel
+            b.w_exp3 = _pack_pw_s3(b.w_exp) if s3 and cin <= MB_S3_MAX_CIN else None
         b.w_dw = sd[bp + "._depthwise_conv.weight"].reshape(b.mid, k, k).permute(1, 2, 0).contiguous()
         b.s1, b.b1 = fold(sd, bp + "._bn1")
         b.se_w1 = sd[bp + "._se_reduce.weight"].reshape(-1, b.mid).contiguous()
@@ -220,6 +226,10 @@ SPLIT3_MIN_OK = 2          # ccvpe_upconv3x3_s3_ok value a layer needs for the r
 # heads (csrc/pw_s3.hip) where the library's size rule prefers it; CCVPE_SPLIT3_PW=0 = conv_igemm (A/B runs), CCVPE_SPLIT3=0 as well
 SPLIT3_PW = SPLIT3 and __import__("os").environ.get("CCVPE_SPLIT3_PW", "1") != "0"
 SPLIT3_PW_MIN_OK = 2       # ccvpe_pw_s3_ok value a layer needs for the route (tests open the size rule with 1)
+# ... and the expand 1x1 inside the fused front kernel of the fp32 early blocks (csrc/mbconv_front.hip: mbconv_front_s3_kernel) where the
+# library's size rule prefers it; CCVPE_SPLIT3_MB=0 = the fp32 front kernel (A/B runs), CCVPE_SPLIT3=0 as well
+SPLIT3_MB = SPLIT3 and __import__("os").environ.get("CCVPE_SPLIT3_MB", "1") != "0"
+SPLIT3_MB_MIN_OK = 2       # ccvpe_mbconv_front_s3_ok value a block needs for the route (tests open the size rule with 1)
 # train mode: replay the per-step weight re-pack as one hipGraph (see _CVMBase._packed); CCVPE_PACK_GRAPH=0 keeps it eager
 PACK_GRAPH = __import__("os").environ.get("CCVPE_PACK_GRAPH", "1") != "0"
 # train mode, fp32: the per-step re-pack as ONE gather launch (ccvpe_amd/repack.py); CCVPE_PACK_GATHER=0 keeps the graph replay
@@ -501,9 +511,14 @@ def _run_encoder(e, img, circular, multiscale, dtype=torch.float32):
                                   out_dtype=dtype)
             b = u.shape[0]
         elif blk.expand and ops.mbconv_front_supported(h, w, blk.cin, blk.mid, blk.k, blk.s):
-            # early blocks: the 6x-expanded tensor stays in LDS (csrc/mbconv_front.hip)
-            u, part = ops.mbconv_front(x, blk.w_exp, blk.s0, blk.b0, blk.w_dw, blk.s1, blk.b1, blk.mid,
-                                       blk.k, blk.s, circular)
+            # early blocks: the 6x-expanded tensor stays in LDS (csrc/mbconv_front.hip); fp32 eval: the expand on the bf16 matrix
+            # cores in three planes where the pack exists and the library's size rule prefers it
+            w3 = getattr(blk, "w_exp3", None)
+            if SPLIT3 and SPLIT3_MB and w3 is not None and ops.mbconv_front_s3_ok(x, w3, blk.mid, blk.k, blk.s) >= SPLIT3_MB_MIN_OK:
+                u, part = ops.mbconv_front_s3(x, w3, blk.s0, blk.b0, blk.w_dw, blk.s1, blk.b1, blk.mid, blk.k, blk.s, circular)
+            else:
+                u, part = ops.mbconv_front(x, blk.w_exp, blk.s0, blk.b0, blk.w_dw, blk.s1, blk.b1, blk.mid,
+                                           blk.k, blk.s, circular)
         else:
             t = x
             if blk.expand:

@@ -633,6 +633,50 @@ def mbconv_front(x, w_exp, s0, b0, w_dw, s1, b1, mid, k, stride, circular):
     return y, part
 
 
+def mbconv_front_s3_ok(x, w_exp3, mid, k, stride):
+    """ccvpe_mbconv_front_s3_ok for this early block: 0 = not served (also: anything but an fp32 x, no three-plane pack or one that
+    is not [ceil(cin / 16)][mid][48] bf16), 1 = the kernel computes it, 2 = and the library's measured size rule prefers it to
+    ccvpe_mbconv_front_f32.  Nothing is launched."""
+    if w_exp3 is None or x.dtype != torch.float32 or w_exp3.dtype != torch.bfloat16:
+        return 0
+    b, h, wd, cin = x.shape
+    if w_exp3.dim() != 3 or tuple(w_exp3.shape) != ((cin + 15) // 16, mid, 48):
+        return 0
+    return int(_lib.load().ccvpe_mbconv_front_s3_ok(h, wd, cin, mid, k, stride, b))
+
+
+def mbconv_front_s3(x, w_exp3, s0, b0, w_dw, s1, b1, mid, k, stride, circular):
+    """mbconv_front's fp32 early block with the expand 1x1 on the bf16 matrix cores, three bf16 planes per fp32 operand
+    (ccvpe_mbconv_front_s3_f32); w_exp3 from models._pack_pw_s3 of the fp32 expand pack.  Same result as mbconv_front to fp32
+    rounding, not bit for bit; same se_partial rows.  A shape the kernel does not serve is an error (no fallback)."""
+    lib = _lib.load()
+    _chk(x, "x", torch.float32)
+    _chk(w_exp3, "w_exp3", torch.bfloat16)
+    for t, nm in ((s0, "s0"), (b0, "b0"), (w_dw, "w_dw"), (s1, "s1"), (b1, "b1")):
+        _chk(t, nm)
+    b, h, wd, cin = x.shape
+    if w_exp3.dim() != 3 or tuple(w_exp3.shape) != ((cin + 15) // 16, mid, 48):
+        raise ValueError("w_exp3 is not the three-plane pack of models._pack_pw_s3 for cin = %d, mid = %d" % (cin, mid))
+    nblk = mbconv_front_supported(h, wd, cin, mid, k, stride)
+    if nblk == 0 or not lib.ccvpe_mbconv_front_s3_ok(h, wd, cin, mid, k, stride, b):
+        raise _lib.CcvpeError("mbconv_front_s3: unsupported shape %s k=%d stride=%d" % (tuple(x.shape), k, stride))
+    tot = (k - 1) if stride == 1 else (k - 2)
+    ho, wo = (h + tot - k) // stride + 1, (wd + tot - k) // stride + 1
+    y = _empty((b, ho, wo, mid), device=x.device, dtype=torch.float32)
+    part = _empty((b, nblk, mid), device=x.device, dtype=torch.float32)
+    rec = _recorder
+    ev0 = rec.begin() if rec is not None else None
+    check(lib.ccvpe_mbconv_front_s3_f32(_ptr(x), _ptr(w_exp3), w_exp3.shape[0] * w_exp3.shape[2], _ptr(s0), _ptr(b0), _ptr(w_dw),
+                                        _ptr(s1), _ptr(b1), _ptr(y), _ptr(part), b, h, wd, cin, mid, k, stride,
+                                        int(bool(circular)), _stream()), "ccvpe_mbconv_front_s3_f32")
+    if rec is not None:
+        # the fp32 layer's FLOPs and bytes (as mbconv_front)
+        flops = 2.0 * b * h * wd * cin * mid + 2.0 * b * ho * wo * mid * k * k
+        nbytes = 4.0 * (b * h * wd * cin + b * ho * wo * mid)
+        rec.end("mbconv_front_s3_kernel<%d,%d>" % (k, stride), "in %dx%dx%d mid %d" % (h, wd, cin, mid), flops, nbytes, ev0)
+    return y, part
+
+
 def se_gate(part, hw, w1, b1, w2, b2):
     lib = _lib.load()
     for t, nm in ((part, "part"), (w1, "w1"), (b1, "b1"), (w2, "w2"), (b2, "b2")):

@@ -346,6 +346,19 @@ int ccvpe_mbconv_front_f32(const float* x, const float* w_exp, int kpad, const f
                            const float* w_dw, const float* s1, const float* b1, float* y, float* se_partial,
                            int batch, int in_h, int in_w, int cin, int mid, int k, int stride, int circular,
                            void* stream);
+/* (ABI 7, additive) The fp32 early blocks with the expand 1x1 on the bf16 matrix cores in the three-plane arithmetic of
+ * ccvpe_upconv3x3_s3_f32 / ccvpe_pw_s3_f32 (csrc/mbconv_front.hip: mbconv_front_s3_kernel): fp32-class error, not bit-identical to
+ * ccvpe_mbconv_front_f32, bit-identical run to run.  Arguments as ccvpe_mbconv_front_f32 except `w_exp3` / `kpad`: the three-plane
+ * pack [ceil(cin / 16)][mid][hi 16 | mid 16 | lo 16] bf16 of the fp32 pack (models._pack_pw_s3), kpad = 48 * ceil(cin / 16).  Tile
+ * geometry and se_partial rows are those of ccvpe_mbconv_front_nblk.  Served: EfficientNet-B0's blocks 1-5, (k, stride, cin) =
+ * (3, 2, <= 16), (3, 1, 17..32), (5, 2, 17..32), (5, 1, 33..48), (3, 2, 33..48).  ccvpe_mbconv_front_s3_ok launches nothing: 0 = not
+ * served (bf16 storage is the caller's to exclude), 1 = computed correctly, 2 = and the measured size rule prefers it to
+ * ccvpe_mbconv_front_f32.  ccvpe_mbconv_front_s3_f32 runs every shape with _ok >= 1 and returns CCVPE_EINVAL otherwise. */
+int ccvpe_mbconv_front_s3_ok(int in_h, int in_w, int cin, int mid, int k, int stride, int batch);
+int ccvpe_mbconv_front_s3_f32(const float* x, const void* w_exp3, int kpad, const float* s0, const float* b0,
+                              const float* w_dw, const float* s1, const float* b1, float* y, float* se_partial,
+                              int batch, int in_h, int in_w, int cin, int mid, int k, int stride, int circular,
+                              void* stream);
 
 /* Squeeze-excite gate: mean -> 1x1 (C->Cs) + swish -> 1x1 (Cs->C) -> sigmoid.
  * efficientnet_pytorch/model.py:113-118.  w1 [Cs][C], w2 TRANSPOSED [Cs][C], gate [B][C]. */
