@@ -67,6 +67,15 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 
+// degrees(acos(c)), reflected as Python's `math.degrees(-a) % 360` when the sine is negative: in [0, 360], where 360.0 is
+// what -a + 360 rounds to for a tiny positive a, in Python as here
+__device__ __forceinline__ double angle_deg_f64(double c, bool neg) {
+  const double a = acos(c) * (180.0 / 3.141592653589793);
+  if (!neg) return a;
+  const double m = fmod(-a, 360.0);
+  return m < 0.0 ? m + 360.0 : 0.0;                              // fmod(-0.0, 360) = -0.0 -> Python's % gives +0.0
+}
+
 typedef float cc_f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 cc_bf16;
 typedef __bf16 cc_bf16x4 __attribute__((ext_vector_type(4)));

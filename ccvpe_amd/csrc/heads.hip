@@ -368,15 +368,6 @@ struct ArgMax {
   }
 };
 
-// degrees(acos(c)), reflected as Python's `math.degrees(-a) % 360` when the sine is negative: in [0, 360], where 360.0 is
-// what -a + 360 rounds to for a tiny positive a, in Python as here
-__device__ __forceinline__ double angle_deg_f64(double c, bool neg) {
-  const double a = acos(c) * (180.0 / 3.141592653589793);
-  if (!neg) return a;
-  const double m = fmod(-a, 360.0);
-  return m < 0.0 ? m + 360.0 : 0.0;                              // fmod(-0.0, 360) = -0.0 -> Python's % gives +0.0
-}
-
 template <bool VEC>
 __global__ __launch_bounds__(1024) void eval_metrics_kernel(const float* __restrict__ heat, const float* __restrict__ ori,
                                                             const float* __restrict__ gt, const float* __restrict__ gto,

@@ -535,6 +535,7 @@ class DeviceBatches(object):
                 training = bool(targets)
             shard = "pad" if (training and world > 1) else "exact"
         self.shard = shard
+        self.shuffle, self.rank, self.world = bool(shuffle), int(rank), int(world)      # how the order was made (evaluate_sequence)
         self.indices = idx[shard_positions(len(idx), world, rank, shard)]
         self.workers, self.prefetch = int(workers), int(prefetch)
         self.grd_hw, self.sat_hw, self.fov = tuple(grd_hw), tuple(sat_hw), fov

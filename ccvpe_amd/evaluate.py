@@ -18,7 +18,8 @@ The reference's full TEST PROTOCOLS (longitudinal / lateral error, recall under 
 ground truth, Oxford's three traversals) are the second half of this file: `evaluate_batches` drives a
 `datasets.DeviceBatches` through the forward and ccvpe_eval_metrics_f32 (twelve doubles per sample, `metrics_spec` is its
 numpy specification), reads ONE table back after the loop, and `summarise` / `format_report` produce what the three test
-scripts print.
+scripts print.  `evaluate_sequence` runs the same protocol along a drive, for the raw heat-maps and for the belief of a
+histogram filter (ccvpe_amd.tracking).
 """
 import math
 
@@ -311,3 +312,59 @@ def evaluate_batches(forward_fn, batches, metres_per_pixel=None, sets=None):
     res = summarise(rows, masks)
     res["rows"], res["indices"] = rows, idx
     return res
+
+
+def evaluate_sequence(forward_fn, batches, filt, shift_px, starts, metres_per_pixel=None, sets=None):
+    """The reference's test protocol along a drive, for the raw heat-maps AND for the belief of a histogram filter
+    (ccvpe_amd.tracking.HistogramFilter with one track).  `batches`: a DeviceBatches in drive order — unshuffled, one rank,
+    targets=True (ValueError otherwise); shift_px [n,2] and starts [n] per sample of `batches.indices`, e.g. from
+    tracking.oxford_shifts(batches.pairs, batches.indices).  Per batch one forward and one ccvpe_eval_metrics_f32 launch for
+    the raw maps; then per frame one `filt.step` (reset first where starts says so) and one ccvpe_eval_metrics_f32 launch on the
+    belief, all into device tables; ONE read-back after the loop.
+    Returns {"raw": summarise(...), "filtered": summarise(...), "tracks": [n,14] (tracking.PRED_Y ... SURVIVED),
+    "raw_rows": [n,12], "filtered_rows": [n,12], "indices": [n]}."""
+    from . import ops
+    if not batches.targets:
+        raise ValueError("evaluate_sequence needs DeviceBatches(..., targets=True): the ground truth comes from the batch")
+    world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
+    idx = np.asarray(batches.indices, dtype=np.int64)
+    # the loader's own settings decide, not the order that came out: a shuffle can leave indices ascending by chance, and a
+    # shard of a larger world is ascending too
+    if world > 1 or batches.world != 1 or batches.shuffle or len(idx) == 0 or np.any(np.diff(idx) <= 0):
+        raise ValueError("evaluate_sequence needs the frames in drive order on one rank: DeviceBatches(..., shuffle=False, "
+                         "world=1) with ascending indices")
+    if filt.n_tracks != 1:
+        raise ValueError("evaluate_sequence steps one track: HistogramFilter(1, ...)")
+    starts = np.asarray(starts).reshape(-1).astype(bool)
+    n = len(idx)
+    if len(starts) != n or len(shift_px) != n:
+        raise ValueError("evaluate_sequence: shift_px and starts must hold one entry per sample of batches.indices (%d)" % n)
+    mpp = default_metres_per_pixel(batches.pairs) if metres_per_pixel is None else metres_per_pixel
+    if sets is None:
+        sets = default_sets(batches.pairs)
+    dev = batches.device
+    shifts = torch.as_tensor(np.asarray(shift_px, dtype=np.float64).reshape(n, 2)).to(dev)
+    raw, fil, trk = (torch.empty((n, c), device=dev, dtype=torch.float64) for c in (12, 12, 14))
+    if not isinstance(mpp, dict):
+        mpp_const = torch.full((max(1, batches.batch_size),), float(mpp), device=dev, dtype=torch.float64)
+    k = 0
+    for batch in batches:
+        b = len(batch.indices)
+        with torch.no_grad():
+            out = forward_fn(batch.grd, batch.sat)
+        m = (torch.tensor([mpp[c] for c in batch.cities], device=dev, dtype=torch.float64) if isinstance(mpp, dict)
+             else mpp_const[:b])
+        heat, ori = out[1], out[2]
+        ops.eval_metrics(heat, ori, batch.gt, batch.gt_ori, batch.heading_deg, m, out=raw[k:k + b])
+        for j in range(b):
+            if starts[k + j]:
+                filt.reset()
+            filt.step(heat[j:j + 1], ori[j:j + 1], shifts[k + j:k + j + 1], rows_out=trk[k + j:k + j + 1])
+            ops.eval_metrics(filt.belief, ori[j:j + 1], batch.gt[j:j + 1], batch.gt_ori[j:j + 1], batch.heading_deg[j:j + 1],
+                             m[j:j + 1], out=fil[k + j:k + j + 1])
+        k += b
+    table = torch.cat([raw, fil, trk], dim=1).cpu().numpy()                      # the one read-back (and the one sync)
+    raw_rows, fil_rows, tracks = table[:, :12], table[:, 12:24], table[:, 24:]
+    masks = {name: np.isin(idx, np.asarray(sel)) for name, sel in sets.items()} if sets else None
+    return {"raw": summarise(raw_rows, masks), "filtered": summarise(fil_rows, masks), "tracks": tracks,
+            "raw_rows": raw_rows, "filtered_rows": fil_rows, "indices": idx}

@@ -897,6 +897,59 @@ def eval_metrics(heatmap, ori, gt, gt_ori, heading_deg, metres_per_pixel, out=No
     return out
 
 
+def belief_partials(h, w):
+    """Doubles of scratch per track that belief_step needs for an h x w grid (launches nothing)."""
+    n = _lib.load().ccvpe_belief_partials(int(h), int(w))
+    if n <= 0:
+        raise ValueError("belief_partials: bad grid %s x %s" % (h, w))
+    return n
+
+
+def belief_step(prior, heatmap, ori, offsets, taps, outlier=0.0, reset=None, post=None, scratch=None, out=None):
+    """One histogram-filter step per track on the device (two launches; ccvpe_amd.tracking.step_spec is the specification):
+    the prior moved by `offsets` [B,2] int32 (oy, ox) and blurred by `taps` [B,2,2R+1] fp32 (y then x, 0 <= R <= 32), times
+    (1 - outlier) * heatmap + outlier / (h w), renormalised.  prior, heatmap [B,1,h,w]; ori [B,2,h,w]; reset [B] int32 or None
+    (a non-zero entry starts that track from the measurement; its prior is not read).  post: a caller's [B,1,h,w] tensor that
+    does not overlap prior; scratch: B * belief_partials(h, w) float64; out: a caller's [B,14] float64 slice of a larger table.
+    Returns (rows [B,14] float64 — columns ccvpe_amd.tracking.PRED_Y ... SURVIVED, post)."""
+    lib = _lib.load()
+    for t, nm in ((prior, "prior"), (heatmap, "heatmap"), (ori, "ori"), (taps, "taps"), (post, "post")):
+        _chk(t, nm)
+    for t, nm in ((offsets, "offsets"), (reset, "reset")):
+        _chk(t, nm, torch.int32)
+    for t, nm in ((scratch, "scratch"), (out, "out")):
+        _chk(t, nm, torch.float64)
+    if heatmap.dim() != 4 or heatmap.shape[1] != 1:
+        raise ValueError("belief_step: heatmap [B,1,h,w] expected, got %s" % (tuple(heatmap.shape),))
+    b, _, h, w = heatmap.shape
+    if prior.shape != heatmap.shape or ori.shape != (b, 2, h, w):
+        raise ValueError("belief_step: prior [B,1,h,w] like heatmap and ori [B,2,h,w] expected")
+    if taps.dim() != 3 or taps.shape[0] != b or taps.shape[1] != 2 or taps.shape[2] % 2 != 1:
+        raise ValueError("belief_step: taps must be [%d,2,2R+1], got %s" % (b, tuple(taps.shape)))
+    radius = (taps.shape[2] - 1) // 2
+    if tuple(offsets.shape) != (b, 2):
+        raise ValueError("belief_step: offsets must be [%d,2], got %s" % (b, tuple(offsets.shape)))
+    if reset is not None and reset.numel() != b:
+        raise ValueError("belief_step: reset must hold one flag per track")
+    need = b * belief_partials(h, w)
+    if scratch is None:
+        scratch = _empty((need,), device=heatmap.device, dtype=torch.float64)
+    elif scratch.numel() < need:
+        raise ValueError("belief_step: scratch holds %d doubles, %d needed" % (scratch.numel(), need))
+    if post is None:
+        post = _empty(tuple(heatmap.shape), device=heatmap.device)
+    elif post.shape != heatmap.shape:
+        raise ValueError("belief_step: post must be %s, got %s" % (tuple(heatmap.shape), tuple(post.shape)))
+    if out is None:
+        out = _empty((b, 14), device=heatmap.device, dtype=torch.float64)
+    elif tuple(out.shape) != (b, 14):
+        raise ValueError("belief_step: out must be [%d,14], got %s" % (b, tuple(out.shape)))
+    check(lib.ccvpe_belief_step_f32(_ptr(prior), _ptr(heatmap), _ptr(ori), _ptr(offsets), _ptr(taps), radius, float(outlier),
+                                    _ptr(reset), _ptr(post), _ptr(scratch), _ptr(out), b, h, w, _stream()),
+          "ccvpe_belief_step_f32")
+    return out, post
+
+
 def _loss_common(fn, name, tensors, extra):
     lib = _lib.load()
     for i, t in enumerate(tensors):

@@ -465,6 +465,31 @@ int ccvpe_eval_metrics_f32(const float* heatmap, const float* ori, const float* 
                            int w, void* stream);
 
 /* -------------------------------------------------------------------------------------------
+ * Sequence localisation: one step of a histogram filter over the heat-map grid, per track b (ccvpe_amd.tracking.step_spec
+ * is the specification, in numpy float64).  Two launches, no host read-back, no allocation, no floating-point atomics
+ * (two runs are bit-identical):
+ *   predict  Q[y,x] = sum_i ky[i+R] sum_j kx[j+R] prior[y - oy - i, x - ox - j], prior = 0 outside the grid (mass that
+ *            leaves the grid is lost; a one-hot prior at (y0,x0) with R = 0 and offset (3,-5) gives Q one-hot at (y0+3, x0-5));
+ *            the row pass, then the column pass, in fp32
+ *   measure  M = (1 - outlier) heat + outlier / (h w);  U = Q M;  Z = sum U, S = sum Q (double)
+ *   reset    1 when reset[b] != 0 (the predict is skipped, S = 0), 2 when not (Z > 0 and finite): U := M, Z := sum M
+ *   post     = U (float)(1 / Z)
+ *   rows[b]  = { pred_y, pred_x (first maximum of U, ties to the smallest index, NaN skipped), post there, cos, sin (ori
+ *                there), angle in degrees (ccvpe_eval_metrics_f32's rule; NaN if |cos| > 1 or |sin| > 1 in float), Z,
+ *                reset (0, 1, 2), mean_y, mean_x, var_yy, var_xx, cov_yx of U / Z over integer pixel coordinates, S }
+ * prior, heat, post [B,h*w] (post must not overlap prior, heat or ori; the prior of a reset track is not read); ori [B,2,h*w];
+ * offsets [B,2] (oy, ox), any int32; taps [B,2,2R+1] (y then x), >= 0; 0 <= radius <= 32; 0 <= outlier <= 1; reset [B] or
+ * NULL; scratch: batch * ccvpe_belief_partials(h, w) doubles (ccvpe_belief_partials launches nothing; CCVPE_EINVAL for a
+ * bad shape); rows [B,14] doubles — any rows of a larger table; rows and scratch 8-byte aligned.  16-byte loads of the prior
+ * when w % 4 == 0 and it is 16-byte aligned, of heat / post when h*w % 4 == 0 and they are.  Non-finite inputs: the call
+ * returns, reset is 2 and the rest of the row is unspecified.
+ * ----------------------------------------------------------------------------------------- */
+int ccvpe_belief_partials(int h, int w);
+int ccvpe_belief_step_f32(const float* prior, const float* heat, const float* ori, const int* offsets, const float* taps,
+                          int radius, float outlier, const int* reset, float* post, double* scratch, double* rows,
+                          int batch, int h, int w, void* stream);
+
+/* -------------------------------------------------------------------------------------------
  * Losses (losses.py:4-29), device scalars out.  `acc` is caller-provided scratch.
  *   infoNCE: accumulates num = sum_{label>1e-2} log(softmax(s/T))*label and den = sum label over
  *            the whole batch; loss = -num/den.            scores/labels [B,n]
