@@ -87,6 +87,11 @@ PROTOTYPES = {
     "ccvpe_set_pwn_kernels": (c_int, [c_int]),
     "ccvpe_conv3x3_wino_ok": (c_int, [ctypes.POINTER(ConvDesc)]),
     "ccvpe_conv3x3_wino_f32": (c_int, [ctypes.POINTER(ConvDesc), c_void_p]),
+    "ccvpe_conv3x3_wino_n_ok": (c_int, [ctypes.POINTER(ConvDesc)]),
+    "ccvpe_conv3x3_wino_n_f32": (c_int, [ctypes.POINTER(ConvDesc), c_void_p]),
+    "ccvpe_conv3x3_wino_match1_ok": (c_int, [ctypes.POINTER(ConvDesc), c_int, c_int]),
+    "ccvpe_conv3x3_wino_match1_f32": (c_int, [ctypes.POINTER(ConvDesc), c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "ccvpe_set_wino_n": (c_int, [c_int]),
     "ccvpe_conv3x3_match1_ok": (c_int, [ctypes.POINTER(ConvDesc), c_int, c_int]),
     "ccvpe_conv3x3_match1_bf16": (c_int, [ctypes.POINTER(ConvDesc), c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "ccvpe_conv_igemm_splitk_f32": (c_int, [ctypes.POINTER(ConvDesc), c_void_p, c_void_p]),
@@ -251,6 +256,8 @@ def load():
         lib.ccvpe_set_pwn_kernels(0)              # A/B runs: the generic kernel for the narrow projections
     if os.environ.get("CCVPE_S3_QUAD") == "0" and hasattr(lib, "ccvpe_set_s3_quad"):
         lib.ccvpe_set_s3_quad(0)                  # A/B runs: the per-parity three-plane upconv kernel on every level
+    if os.environ.get("CCVPE_WINO_N") == "0" and hasattr(lib, "ccvpe_set_wino_n"):
+        lib.ccvpe_set_wino_n(0)                   # A/B runs: conv3x3_wino_kernel + match_level on the narrow fp32 levels
     if os.environ.get("CCVPE_MBPLANE") is not None and hasattr(lib, "ccvpe_set_mbconv_plane_kernels"):
         lib.ccvpe_set_mbconv_plane_kernels(int(os.environ["CCVPE_MBPLANE"]))   # A/B runs: 0 = pointwise GEMM + dwconv_plane_kernel
     _lib = lib

@@ -235,8 +235,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wino_kernel(const IgemmParams 
 
 static int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
-// the shapes the kernel serves; the reason for a refusal (or nullptr)
-static const char* wino_refusal(const ccvpe_conv_desc* d) {
+// the shapes the kernels of this family compute correctly; the reason for a refusal (or nullptr)
+const char* wino_shape_refusal(const ccvpe_conv_desc* d) {
   if (!d) return "null desc";
   if (d->kh != 3 || d->kw != 3 || d->stride != 1 || d->pad != 1 || d->out_mode != CCVPE_OUT_NHWC) return "3x3 / stride 1 / pad 1 / NHWC only";
   if (d->c1 != 0 || d->src1 || d->gate || d->scale || d->residual || d->act != CCVPE_ACT_NONE)
@@ -245,10 +245,18 @@ static const char* wino_refusal(const ccvpe_conv_desc* d) {
   if (d->c0 < 32 || d->c0 % 4 || d->ld0 < d->c0 || d->ld0 % 4) return "c0 >= 32, c0 and ld0 multiples of 4";
   if (d->n <= 0 || d->ldd < d->n || d->ldd % 4) return "ldd >= n, ldd multiple of 4";
   if (d->kpad != 16 * round_up(d->c0, 16)) return "kpad must be 16 * round_up(c0, 16) (packed U)";
-  if ((long)d->batch * d->in_h * d->in_w < 16384) return "fewer than 16384 output pixels";
+  if (d->batch <= 0) return "batch must be positive";
   if ((long)d->batch * d->in_h * d->in_w > 0x7fffffffL) return "too many pixels";
   if ((size_t)round_up(d->n, WG_BN) * d->kpad * 4 >= (1ull << 32)) return "U larger than 4 GB";
   if (!aligned16(d->src0) || !aligned16(d->w) || !aligned16(d->dst)) return "pointers must be 16-byte aligned";
+  return nullptr;
+}
+
+// ... and the size rule on top: the launches where Winograd is the faster route (ccvpe_conv3x3_wino_ok; the launchers themselves
+// run any shape they compute correctly)
+const char* wino_refusal(const ccvpe_conv_desc* d) {
+  if (const char* why = wino_shape_refusal(d)) return why;
+  if ((long)d->batch * d->in_h * d->in_w < 16384) return "fewer than 16384 output pixels";
   // where the direct path would split K (small batch), the split wins: stay with it
   ccvpe_conv_desc dd = *d;
   dd.kpad = round_up(9 * d->c0, 16);
@@ -263,7 +271,7 @@ using namespace ccvpe;
 extern "C" int ccvpe_conv3x3_wino_ok(const ccvpe_conv_desc* d) { return wino_refusal(d) ? 0 : 1; }
 
 extern "C" int ccvpe_conv3x3_wino_f32(const ccvpe_conv_desc* d, void* stream) {
-  if (const char* why = wino_refusal(d)) return fail(CCVPE_EINVAL, "conv3x3_wino: %s", why);
+  if (const char* why = wino_shape_refusal(d)) return fail(CCVPE_EINVAL, "conv3x3_wino: %s", why);
   IgemmParams p{};
   p.src0 = d->src0; p.w = d->w; p.shift = d->shift; p.dst = d->dst;
   p.c0 = d->c0; p.ld0 = d->ld0;

@@ -290,6 +290,9 @@ bool pwn_supported(const IgemmParams& p, int batch, int esz);
 int pwn_dispatch(const IgemmParams& p, int batch, int esz, hipStream_t stream);
 int up2_supported(int c0, int c1, int n, int kpad, int h1, int w1, int batch);      // 0 = not served, else an instantiation id
 int up2_launch(int id, const ccvpe_upconv_desc* d, hipStream_t stream);
+// conv3x3_wino.hip: why the Winograd kernels do not compute `d` correctly / why they are not the faster route for it (nullptr: they are)
+const char* wino_shape_refusal(const ccvpe_conv_desc* d);
+const char* wino_refusal(const ccvpe_conv_desc* d);
 // upconv_s3q.hip: the four-parities-per-workgroup form of upconv_s3.hip's layer, for a desc that file's s3_pick() has accepted
 bool upconv_s3q_serves(const ccvpe_upconv_desc* d);
 int upconv_s3q_launch(const ccvpe_upconv_desc* d, hipStream_t stream);      // (a desc s3_pick() routed to the quad form)

@@ -48,6 +48,7 @@ static const std::unordered_map<std::string, Invoker>& registry() {
   static const std::unordered_map<std::string, Invoker> r = {
       CCVPE_REG(ccvpe_conv_igemm_f32), CCVPE_REG(ccvpe_conv_igemm_bf16), CCVPE_REG(ccvpe_conv_igemm_splitk_f32),
       CCVPE_REG(ccvpe_conv_igemm_splitk_bf16), CCVPE_REG(ccvpe_conv3x3_match1_bf16), CCVPE_REG(ccvpe_conv3x3_wino_f32),
+      CCVPE_REG(ccvpe_conv3x3_wino_n_f32), CCVPE_REG(ccvpe_conv3x3_wino_match1_f32),
       CCVPE_REG(ccvpe_upconv3x3_f32), CCVPE_REG(ccvpe_upconv3x3_bf16), CCVPE_REG(ccvpe_upconv3x3_s3_f32), CCVPE_REG(ccvpe_pw_s3_f32),
       CCVPE_REG(ccvpe_tail512_f32), CCVPE_REG(ccvpe_tail512_bf16), CCVPE_REG(ccvpe_stem_conv_f32), CCVPE_REG(ccvpe_stem_conv_bf16),
       CCVPE_REG(ccvpe_stem_dw_f32), CCVPE_REG(ccvpe_stem_dw_bf16),

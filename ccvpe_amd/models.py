@@ -236,6 +236,9 @@ PACK_GRAPH = __import__("os").environ.get("CCVPE_PACK_GRAPH", "1") != "0"
 PACK_GATHER = __import__("os").environ.get("CCVPE_PACK_GATHER", "1") != "0"
 # one-hypothesis matching of level j + 1 inside level j's last conv (bf16 narrow levels); CCVPE_FUSE_MATCH=0 = separate launches (A/B runs)
 FUSE_MATCH = __import__("os").environ.get("CCVPE_FUSE_MATCH", "1") != "0"
+# fp32 convK.2 layers of at most 80 channels: all columns in one workgroup, with the one-hypothesis matching fused on the localisation
+# levels (csrc/conv3x3_wino_n.hip), where the library's size rule prefers it; CCVPE_WINO_N=0 = conv3x3_wino + match_level (A/B runs)
+WINO_N_MIN_OK = 2          # ccvpe_conv3x3_wino_n_ok / _wino_match1_ok value a layer needs for the route (tests open the size rule with 1)
 # stem conv + block-0 depthwise conv as one launch (csrc/stem_dw.hip); CCVPE_FUSE_STEM=0 = the two unfused launches (A/B runs)
 FUSE_STEM = __import__("os").environ.get("CCVPE_FUSE_STEM", "1") != "0"
 # eval forward: CCVPE_EVAL_TWO_STREAMS=0 runs the ground encoder on the main stream too (for per-kernel profiles in which no
@@ -547,7 +550,11 @@ def _double_conv(lv, up, skip, batch, hw):
 
 def _conv_b(lv, y, batch, hw, out_f32=False):
     """convK.2 of double_conv (3x3, bias, no activation): Winograd F(2x2,3x3) where the library serves the layer (fp32
-    storage, csrc/conv3x3_wino.hip), else the direct 3x3 kernel."""
+    storage, csrc/conv3x3_wino.hip; at most 80 channels: its one-workgroup-per-tile form, csrc/conv3x3_wino_n.hip), else the
+    direct 3x3 kernel."""
+    if (WINO and lv.u_b is not None and
+            ops.conv3x3_wino_n_ok(y, lv.n_a, lv.u_b, lv.n_b, batch=batch, in_h=hw, in_w=hw) >= WINO_N_MIN_OK):
+        return ops.conv3x3_wino_n(y, lv.n_a, lv.u_b, lv.n_b, batch=batch, in_h=hw, in_w=hw, shift=lv.b_b)
     if (WINO and lv.u_b is not None and
             ops.conv3x3_wino_ok(y, lv.n_a, lv.u_b, lv.n_b, batch=batch, in_h=hw, in_w=hw)):
         return ops.conv3x3_wino(y, lv.n_a, lv.u_b, lv.n_b, batch=batch, in_h=hw, in_w=hw, shift=lv.b_b)
@@ -887,7 +894,15 @@ class _CVMBase(nn.Module):
                     to_f32 = j + 1 == pk.f32_from and y.dtype != torch.float32
                     nxt = pk.loc[j + 1]
                     L_n = gw * spec["cd"][j + 1]
-                    if (FUSE_MATCH and len(loc_shifts) == 1 and
+                    if (FUSE_MATCH and WINO and len(loc_shifts) == 1 and y.dtype == torch.float32 and lv.u_b is not None and
+                            ops.conv3x3_match1(y, lv.n_a, lv.u_b, lv.n_b, None, L_n, loc_shifts[0], strides[j + 1], nxt.ldo, batch=batch,
+                                               in_h=2 * hw, in_w=2 * hw, bias=lv.b_b, query_only=True) >= WINO_N_MIN_OK):
+                        # fp32: the same fusion in the Winograd kernel that holds all of a pixel's channels (csrc/conv3x3_wino_n.hip)
+                        fused = ops.conv3x3_match1(y, lv.n_a, lv.u_b, lv.n_b, gdesc[:, goff:goff + L_n], L_n, loc_shifts[0],
+                                                   strides[j + 1], nxt.ldo, batch=batch, in_h=2 * hw, in_w=2 * hw, bias=lv.b_b,
+                                                   window_offset=window_offset(self.kind, nxt.c, L_n))
+                        x = fused[1]
+                    elif (FUSE_MATCH and len(loc_shifts) == 1 and
                             ops.conv3x3_match1(y, lv.n_a, lv.w_b, lv.n_b, None, L_n, loc_shifts[0], strides[j + 1], nxt.ldo, batch=batch,
                                                in_h=2 * hw, in_w=2 * hw, bias=lv.b_b, out_f32=to_f32, query_only=True)):
                         # one rotation hypothesis (ori_prior(0)): the next level's matching rides in this conv's epilogue

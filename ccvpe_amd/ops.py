@@ -295,6 +295,69 @@ def conv3x3_wino(src0, c0, u_packed, n, *, batch, in_h, in_w, shift=None, dst=No
     return dst
 
 
+def conv3x3_wino_n_ok(src0, c0, u_packed, n, *, batch, in_h, in_w, ldd=None, ld0=None):
+    """ccvpe_conv3x3_wino_n_ok for this layer: 0 = not served, 1 = computed correctly, 2 = also a launch the probe showed a win at."""
+    if src0.dtype != torch.float32 or u_packed is None:
+        return 0
+    ld0 = ld0 if ld0 is not None else src0.shape[-1]
+    d = _wino_desc(src0, c0, u_packed, n, batch, in_h, in_w, None, None, ldd if ldd is not None else n, ld0)
+    return int(_lib.load().ccvpe_conv3x3_wino_n_ok(ctypes.byref(d)))
+
+
+def conv3x3_wino_n(src0, c0, u_packed, n, *, batch, in_h, in_w, shift=None, dst=None, ldd=None, ld0=None):
+    """conv3x3_wino for 16 < n <= 80 with all output channels in one workgroup (ccvpe_conv3x3_wino_n_f32): bit-identical to
+    conv3x3_wino.  A shape the kernel does not serve is an error."""
+    lib = _lib.load()
+    for t, nm in ((src0, "src0"), (u_packed, "w"), (shift, "shift"), (dst, "dst")):
+        _chk(t, nm)
+    ld0 = ld0 if ld0 is not None else src0.shape[-1]
+    if dst is None:
+        ldd = ldd if ldd is not None else n
+        dst = _empty((batch, in_h, in_w, ldd), device=src0.device)
+    elif ldd is None:
+        ldd = dst.shape[-1]
+    d = _wino_desc(src0, c0, u_packed, n, batch, in_h, in_w, shift, dst, ldd, ld0)
+    rec = _recorder
+    ev0 = rec.begin() if rec is not None else None
+    check(lib.ccvpe_conv3x3_wino_n_f32(ctypes.byref(d), _stream()), "ccvpe_conv3x3_wino_n_f32")
+    if rec is not None:
+        m = batch * in_h * in_w
+        flops = 2.0 * m * n * 9 * c0                   # the direct algorithm's, as conv3x3_wino
+        nbytes = 4.0 * (m * c0 + m * n + n * 9 * c0)
+        rec.end("conv3x3_wino_n_kernel<%d>" % (-(-n // 16)), "3x3 s1 M%d N%d K%d" % (m, n, 9 * c0), flops, nbytes, ev0)
+    return dst
+
+
+def _conv3x3_match1_f32(src0, c0, u_packed, n, g, L, shift, stride, ldo, batch, in_h, in_w, bias, window_offset, query_only):
+    """fp32 storage: the Winograd kernel with all n <= 80 channels in one workgroup (ccvpe_conv3x3_wino_match1_f32); u_packed from
+    models._pack_wino.  query_only returns the library's 0 / 1 / 2."""
+    lib = _lib.load()
+    if u_packed is None or u_packed.dtype != torch.float32 or src0.dtype != torch.float32:
+        if query_only:
+            return 0
+        raise ValueError("conv3x3_match1: fp32 storage needs the Winograd U pack")
+    _chk(src0, "src0")
+    _chk(u_packed, "w")
+    _chk(bias, "bias")
+    d = _wino_desc(src0, c0, u_packed, n, batch, in_h, in_w, bias, None, ldo, src0.shape[-1])
+    if query_only:
+        return int(lib.ccvpe_conv3x3_wino_match1_ok(ctypes.byref(d), 1, L))
+    if not g.is_cuda or g.dtype != torch.float32 or g.stride(-1) != 1:
+        raise ValueError("g must be an fp32 device tensor with unit inner stride")
+    scores = _empty((batch, 1, in_h, in_w), device=src0.device, dtype=torch.float32)
+    cat = _empty((batch, in_h, in_w, ldo), device=src0.device, dtype=torch.float32)
+    d.dst = _ptr(cat)
+    rec = _recorder
+    ev0 = rec.begin() if rec is not None else None
+    check(lib.ccvpe_conv3x3_wino_match1_f32(ctypes.byref(d), 1, _ptr(g), g.stride(0), L, int(shift), int(stride),
+                                            int(window_offset), _ptr(scores), _stream()), "ccvpe_conv3x3_wino_match1_f32")
+    if rec is not None:
+        m = batch * in_h * in_w
+        rec.end("conv3x3_wino_n_kernel<%d,match>" % (-(-n // 16)), "3x3+match M%d N%d K%d" % (m, n, 9 * c0), 2.0 * m * n * 9 * c0,
+                4.0 * m * c0 + 4.0 * m * ldo + 4.0 * m + 4.0 * n * 9 * c0, ev0)
+    return scores, cat
+
+
 def upconv3x3(src0, c0, w_packed, shift9, n, *, batch, h1, w1, src1=None, c1=0, act=ACT_NONE, algo_flops=None, route_only=False):
     """ConvTranspose2d(k2,s2) folded into the following 3x3 conv (ccvpe_upconv3x3_f32 / _bf16).
     src0 [B,h1,w1,ld0] low-res, src1 [B,2h1,2w1,ld1] skip; returns [B,2h1,2w1,n]."""
@@ -706,13 +769,13 @@ def conv3x3_match1(src0, c0, w_packed, n, g, L, shift, stride, ldo, *, batch, in
     """convK.2 (3x3, bias, no activation) of a decoder level WITH the next level's one-hypothesis matching in its epilogue
     (ccvpe_conv3x3_match1_bf16, csrc/narrow_impl.h c3n_kernel<MATCH>): returns (scores [B,1,H,W] fp32, cat [B,H,W,ldo] bf16 / fp32)
     = what conv_igemm(...) followed by match_level(x, g, L, [shift], 1, 0, stride, ldo) returns; x is never written.
-    query_only: True / False — does the library serve this layer and shape (else the caller runs the two ops)."""
+    query_only: True / False — does the library serve this layer and shape (else the caller runs the two ops).
+    fp32 storage: w_packed is the Winograd U pack (models._pack_wino) and the launch is ccvpe_conv3x3_wino_match1_f32
+    (csrc/conv3x3_wino_n.hip); query_only then returns that entry's 0 / 1 / 2 (served at all / ... and a measured win)."""
     lib = _lib.load()
     dt = _act_dtype(src0)
     if dt != torch.bfloat16:
-        if query_only:
-            return False
-        raise ValueError("conv3x3_match1: bf16 storage only")
+        return _conv3x3_match1_f32(src0, c0, w_packed, n, g, L, shift, stride, ldo, batch, in_h, in_w, bias, window_offset, query_only)
     _chk(src0, "src0", dt)
     _chk(w_packed, "w", dt)
     _chk(bias, "bias")

@@ -26,13 +26,13 @@ ALIGN = 256
 
 # entry points a plan may contain (csrc/plan.hip's registry); everything else the forward calls is a host-side query
 LAUNCHES = ("ccvpe_conv_igemm_f32", "ccvpe_conv_igemm_bf16", "ccvpe_conv_igemm_splitk_f32", "ccvpe_conv_igemm_splitk_bf16",
-            "ccvpe_conv3x3_match1_bf16", "ccvpe_conv3x3_wino_f32",
+            "ccvpe_conv3x3_match1_bf16", "ccvpe_conv3x3_wino_f32", "ccvpe_conv3x3_wino_n_f32", "ccvpe_conv3x3_wino_match1_f32",
             "ccvpe_upconv3x3_f32", "ccvpe_upconv3x3_bf16", "ccvpe_upconv3x3_s3_f32", "ccvpe_pw_s3_f32", "ccvpe_tail512_f32", "ccvpe_tail512_bf16", "ccvpe_stem_conv_f32",
             "ccvpe_stem_conv_bf16", "ccvpe_stem_dw_f32", "ccvpe_stem_dw_bf16", "ccvpe_dwconv_f32", "ccvpe_dwconv_bf16", "ccvpe_mbconv_front_f32", "ccvpe_mbconv_front_bf16", "ccvpe_mbconv_front_s3_f32",
             "ccvpe_se_gate_f32", "ccvpe_ground_descriptor_f32", "ccvpe_match_level_f32", "ccvpe_match_level_bf16",
             "ccvpe_head_conv3x3_f32", "ccvpe_head_conv3x3_bf16", "ccvpe_softmax_rows_f32", "ccvpe_softmax_apply_f32", "ccvpe_cast_bf16_f32",
             "ccvpe_eval_postprocess_f32")
-QUERIES = ("ccvpe_tail512_partials", "ccvpe_conv3x3_match1_ok", "ccvpe_conv3x3_wino_ok", "ccvpe_upconv3x3_s3_ok", "ccvpe_conv_igemm_splitk_floats", "ccvpe_conv_igemm_route", "ccvpe_conv3x3_variant", "ccvpe_upconv3x3_route", "ccvpe_upconv3x3_s3_route", "ccvpe_pw_s3_ok", "ccvpe_pw_s3_route", "ccvpe_dwconv_nblk", "ccvpe_mbconv_front_nblk", "ccvpe_mbconv_front_route", "ccvpe_mbconv_front_s3_ok", "ccvpe_mbconv_band_plan", "ccvpe_stem_dw_nblk",
+QUERIES = ("ccvpe_tail512_partials", "ccvpe_conv3x3_match1_ok", "ccvpe_conv3x3_wino_ok", "ccvpe_conv3x3_wino_n_ok", "ccvpe_conv3x3_wino_match1_ok", "ccvpe_upconv3x3_s3_ok", "ccvpe_conv_igemm_splitk_floats", "ccvpe_conv_igemm_route", "ccvpe_conv3x3_variant", "ccvpe_upconv3x3_route", "ccvpe_upconv3x3_s3_route", "ccvpe_pw_s3_ok", "ccvpe_pw_s3_route", "ccvpe_dwconv_nblk", "ccvpe_mbconv_front_nblk", "ccvpe_mbconv_front_route", "ccvpe_mbconv_front_s3_ok", "ccvpe_mbconv_band_plan", "ccvpe_stem_dw_nblk",
            "ccvpe_last_error", "ccvpe_abi_version")
 
 

@@ -143,6 +143,19 @@ int ccvpe_set_mbconv_plane_kernels(int mode);
  * c0 >= 32, batch * H * W >= 16384, not a shape the direct path splits along K), else 0 — then use ccvpe_conv_igemm_f32. */
 int ccvpe_conv3x3_wino_ok(const ccvpe_conv_desc* desc);
 int ccvpe_conv3x3_wino_f32(const ccvpe_conv_desc* desc, void* stream);
+/* The same layer with all of its n <= 80 output channels in ONE workgroup (csrc/conv3x3_wino_n.hip): one input transform per tile
+ * instead of one per 32 columns, 16-column granular matrix work; bit-identical to ccvpe_conv3x3_wino_f32.  desc and U pack as
+ * above, 16 < n <= 80.  _ok: 0 = not served, 1 = computed correctly, 2 = also at or above the smallest launch at which
+ * tools/wino_probe.py showed a win over ccvpe_conv3x3_wino_f32 (what models.py routes).  ccvpe_conv3x3_wino_match1_*: that kernel
+ * with the next level's one-hypothesis matching in its epilogue — arguments and results exactly as ccvpe_conv3x3_match1_bf16
+ * (below) in fp32 storage with the U pack as `w`; needs n % 4 == 0, ldd >= n + 1, 0 < L <= n.  ccvpe_set_wino_n(0) caps both
+ * _ok values at 1 (A/B runs; the binding calls it for CCVPE_WINO_N=0); returns the previous setting. */
+int ccvpe_conv3x3_wino_n_ok(const ccvpe_conv_desc* desc);
+int ccvpe_conv3x3_wino_n_f32(const ccvpe_conv_desc* desc, void* stream);
+int ccvpe_conv3x3_wino_match1_ok(const ccvpe_conv_desc* desc, int out_f32, int L);
+int ccvpe_conv3x3_wino_match1_f32(const ccvpe_conv_desc* desc, int out_f32, const float* g, int ldg, int L, int shift, int stride,
+                                  int window_offset, float* scores, void* stream);
+int ccvpe_set_wino_n(int on);
 int ccvpe_conv3x3_match1_ok(const ccvpe_conv_desc* desc, int out_f32, int L);
 int ccvpe_conv3x3_match1_bf16(const ccvpe_conv_desc* desc, int out_f32, const float* g, int ldg, int L, int shift, int stride,
                               int window_offset, float* scores, void* stream);
