@@ -10,6 +10,9 @@
 // Launch two, belief_finish_kernel: every workgroup of a track merges the track's records in the same fixed order, decides
 // the reset, scales its slice of the map by (float)(1 / Z), and the first slice writes the row.
 // No floating-point atomics: two runs are bit-identical.
+// The rigid step (ccvpe_belief_step_rigid_f32; tracking.step_rigid_spec) replaces only the staging of launch one:
+// belief_predict_rigid_kernel fills the LDS tile with the prior resampled bilinearly through the track's inverse motion map and
+// then runs the same passes (bf_blur_measure); launch two is the same kernel.
 #include "common.h"
 
 namespace ccvpe {
@@ -60,6 +63,11 @@ __device__ __forceinline__ void bf_moments(double* m, float v, int y, int x) {
   m[5] = fma(d * dy, dx, m[5]);
 }
 
+__device__ __forceinline__ void bf_blur_measure(const float* T, float* mid, const float* __restrict__ heat,
+                                                const float* __restrict__ taps, int R, float one_minus_a, float floor_m,
+                                                bool skip, float* __restrict__ post, double* __restrict__ scratch, int b,
+                                                int tile, int ntiles, int y0, int x0, int h, int w);
+
 template <bool VEC>
 __global__ __launch_bounds__(256) void belief_predict_kernel(const float* __restrict__ prior, const float* __restrict__ heat,
                                                              const int* __restrict__ offsets, const float* __restrict__ taps,
@@ -67,14 +75,11 @@ __global__ __launch_bounds__(256) void belief_predict_kernel(const float* __rest
                                                              const int* __restrict__ reset, float* __restrict__ post,
                                                              double* __restrict__ scratch, int h, int w, int ntx, int nty) {
   extern __shared__ cc_f32x4 bf_smem[];
-  __shared__ double red[4][BF_NSUM];
-  __shared__ float rv[2][4];
-  __shared__ int ri[2][4];
   const int tid = threadIdx.x;
   const int ntiles = ntx * nty;
   const int b = blockIdx.x / ntiles, tile = blockIdx.x - b * ntiles;
   const int y0 = (tile / ntx) * BF_TH, x0 = (tile % ntx) * BF_TW;
-  const int rows = BF_TH + 2 * R, PW = bf_pitch(R), K = 2 * R + 1;
+  const int rows = BF_TH + 2 * R, PW = bf_pitch(R);
   float* T = reinterpret_cast<float*>(bf_smem);                  // [rows][PW]: T[r][c] = prior(y0 + r - R - oy, x0 + c - R - ox)
   float* mid = T + rows * PW;                                    // [rows][BF_TW]: the row pass
   const bool skip = reset != nullptr && reset[b] != 0;           // a reset track starts from the measurement: no predict
@@ -113,6 +118,21 @@ __global__ __launch_bounds__(256) void belief_predict_kernel(const float* __rest
       }
     }
   }
+  bf_blur_measure(T, mid, heat, taps, R, one_minus_a, floor_m, skip, post, scratch, b, tile, ntiles, y0, x0, h, w);
+}
+
+// Everything after the staging of T (the moved prior of the tile with its R halo), for both predict kernels: the barrier, the
+// row pass, the column pass, the measure, U and the tile's record.
+__device__ __forceinline__ void bf_blur_measure(const float* T, float* mid, const float* __restrict__ heat,
+                                                const float* __restrict__ taps, int R, float one_minus_a, float floor_m,
+                                                bool skip, float* __restrict__ post, double* __restrict__ scratch, int b,
+                                                int tile, int ntiles, int y0, int x0, int h, int w) {
+  __shared__ double red[4][BF_NSUM];
+  __shared__ float rv[2][4];
+  __shared__ int ri[2][4];
+  const int tid = threadIdx.x;
+  const int rows = BF_TH + 2 * R, PW = bf_pitch(R), K = 2 * R + 1;
+  const size_t n = (size_t)h * w;
   __syncthreads();
   if (!skip) {
     // row pass: mid[r][x] = sum_j kx[2R - j] T[r][x + j], four consecutive x per lane from 16-byte pieces of the row
@@ -210,6 +230,68 @@ __global__ __launch_bounds__(256) void belief_predict_kernel(const float* __rest
     rec[15] = (double)am.v; rec[16] = (double)am.i;
     rec[17] = 0.0;
   }
+}
+
+// (a0 y + a1 x) + a2 with every product and every sum rounded on its own, as numpy evaluates the specification's expression.
+// The operators are written out under contract(off): __dmul_rn / __dadd_rn are plain inline `*` and `+` in this toolchain, and
+// the compiler fuses them into a multiply-add across the call (seen in the ISA) — the pragma only governs what it encloses.
+__device__ __forceinline__ double bf_affine(double a0, double a1, double a2, double y, double x) {
+#pragma clang fp contract(off)
+  const double p = a0 * y;
+  const double q = a1 * x;
+  const double s = p + q;
+  return s + a2;
+}
+
+// Launch one of the rigid step (tracking.step_rigid_spec): T holds W, the bilinear sample of the prior through the track's
+// inverse map, on the (16 + 2R) x (64 + 2R) pixels the tile's blur reads — the halo is warped too, the blur runs over W.  The
+// source coordinates are computed per sample in double from the integer pixel with separately rounded products and sums in the
+// order of the specification (no contraction, no stepping), so floor() and the fp32 weights are the specification's; the range
+// test is done on the doubles (any motion row, NaN and inf included, reads nothing outside the prior).  The four taps are
+// gathered from global memory (1 MB per track at 512 x 512: L2-resident, 2-D local); columns of T beyond 64 + 2R are loaded by
+// the row pass but enter no sum.
+__global__ __launch_bounds__(256) void belief_predict_rigid_kernel(const float* __restrict__ prior, const float* __restrict__ heat,
+                                                                   const double* __restrict__ motion, const float* __restrict__ taps,
+                                                                   int R, float one_minus_a, float floor_m,
+                                                                   const int* __restrict__ reset, float* __restrict__ post,
+                                                                   double* __restrict__ scratch, int h, int w, int ntx, int nty) {
+  extern __shared__ cc_f32x4 bf_smem[];
+  const int tid = threadIdx.x;
+  const int ntiles = ntx * nty;
+  const int b = blockIdx.x / ntiles, tile = blockIdx.x - b * ntiles;
+  const int y0 = (tile / ntx) * BF_TH, x0 = (tile % ntx) * BF_TW;
+  const int rows = BF_TH + 2 * R, cols = BF_TW + 2 * R, PW = bf_pitch(R);
+  float* T = reinterpret_cast<float*>(bf_smem);                  // [rows][PW]: T[r][c] = W(y0 + r - R, x0 + c - R), c < cols
+  float* mid = T + rows * PW;
+  const bool skip = reset != nullptr && reset[b] != 0;
+  if (!skip) {
+    const double* m = motion + (size_t)b * 6;
+    const double a00 = m[0], a01 = m[1], a02 = m[2], a10 = m[3], a11 = m[4], a12 = m[5];
+    const double hd = (double)h, wd = (double)w;
+    const float* pb = prior + (size_t)b * h * w;
+    for (int idx = tid; idx < rows * cols; idx += 256) {
+      const int r = idx / cols, c = idx - r * cols;
+      const double y = (double)(y0 + r - R), x = (double)(x0 + c - R);
+      const double sy = bf_affine(a00, a01, a02, y, x), sx = bf_affine(a10, a11, a12, y, x);
+      float v = 0.f;
+      if (sy > -1.0 && sy < hd && sx > -1.0 && sx < wd) {        // false for NaN and inf; only then to int
+        const double fy0 = floor(sy), fx0 = floor(sx);
+        const double fy = sy - fy0, fx = sx - fx0;
+        const int iy = (int)fy0, ix = (int)fx0;                  // -1 .. h - 1, -1 .. w - 1
+        const float wy1 = (float)fy, wy0 = (float)(1.0 - fy);
+        const float wx1 = (float)fx, wx0 = (float)(1.0 - fx);
+        const bool ya = iy >= 0, yb = iy + 1 < h, xa = ix >= 0, xb = ix + 1 < w;
+        const long long e = (long long)iy * w + ix;              // dereferenced only under the guards
+        const float v00 = (ya && xa) ? pb[e] : 0.f, v01 = (ya && xb) ? pb[e + 1] : 0.f;
+        const float v10 = (yb && xa) ? pb[e + w] : 0.f, v11 = (yb && xb) ? pb[e + w + 1] : 0.f;
+        const float top = fmaf(wx1, v01, __fmul_rn(wx0, v00));
+        const float bot = fmaf(wx1, v11, __fmul_rn(wx0, v10));
+        v = fmaf(wy1, bot, __fmul_rn(wy0, top));
+      }
+      T[r * PW + c] = v;
+    }
+  }
+  bf_blur_measure(T, mid, heat, taps, R, one_minus_a, floor_m, skip, post, scratch, b, tile, ntiles, y0, x0, h, w);
 }
 
 template <bool VEC>
@@ -328,21 +410,24 @@ extern "C" int ccvpe_belief_partials(int h, int w) {
   return ntx * nty * BF_REC;
 }
 
-extern "C" int ccvpe_belief_step_f32(const float* prior, const float* heat, const float* ori, const int* offsets,
-                                     const float* taps, int radius, float outlier, const int* reset, float* post,
-                                     double* scratch, double* rows, int batch, int h, int w, void* stream) {
-  int ntx, nty;
-  if (batch <= 0 || !bf_tiles(h, w, &ntx, &nty)) return fail(CCVPE_EINVAL, "belief_step: bad shape");
-  const long long ntiles = (long long)ntx * nty;
+
+namespace ccvpe {
+
+// The argument checks the two step entry points share; `move` is the step's own motion input (offsets / motion).
+static int bf_check(const float* prior, const float* heat, const float* ori, const void* move, const float* taps, int radius,
+                    float outlier, const int* reset, float* post, double* scratch, double* rows, int batch, int h, int w,
+                    int* ntx, int* nty) {
+  if (batch <= 0 || !bf_tiles(h, w, ntx, nty)) return fail(CCVPE_EINVAL, "belief_step: bad shape");
+  const long long ntiles = (long long)*ntx * *nty;
   if (ntiles * batch > 0x7fffffffLL) return fail(CCVPE_EINVAL, "belief_step: batch x tiles > 2^31");
   if (radius < 0 || radius > 32) return fail(CCVPE_EINVAL, "belief_step: radius %d outside [0, 32]", radius);
   if (!(outlier >= 0.f && outlier <= 1.f)) return fail(CCVPE_EINVAL, "belief_step: outlier outside [0, 1]");
-  if (!prior || !heat || !ori || !offsets || !taps || !post || !scratch || !rows)
+  if (!prior || !heat || !ori || !move || !taps || !post || !scratch || !rows)
     return fail(CCVPE_EINVAL, "belief_step: null pointer");
   if ((reinterpret_cast<uintptr_t>(rows) | reinterpret_cast<uintptr_t>(scratch)) & 7)
     return fail(CCVPE_EINVAL, "belief_step: rows and scratch must be 8-byte aligned");
   if ((reinterpret_cast<uintptr_t>(prior) | reinterpret_cast<uintptr_t>(heat) | reinterpret_cast<uintptr_t>(ori) |
-       reinterpret_cast<uintptr_t>(post) | reinterpret_cast<uintptr_t>(offsets) | reinterpret_cast<uintptr_t>(taps) |
+       reinterpret_cast<uintptr_t>(post) | reinterpret_cast<uintptr_t>(move) | reinterpret_cast<uintptr_t>(taps) |
        reinterpret_cast<uintptr_t>(reset)) & 3)
     return fail(CCVPE_EINVAL, "belief_step: float and int arrays must be 4-byte aligned");
   const size_t n = (size_t)h * w, bytes = (size_t)batch * n * sizeof(float);
@@ -352,6 +437,40 @@ extern "C" int ccvpe_belief_step_f32(const float* prior, const float* heat, cons
   const uintptr_t h0 = reinterpret_cast<uintptr_t>(heat), o0 = reinterpret_cast<uintptr_t>(ori);
   if (h0 < q0 + bytes && q0 < h0 + bytes) return fail(CCVPE_EINVAL, "belief_step: heat and post overlap");
   if (o0 < q0 + bytes && q0 < o0 + 2 * bytes) return fail(CCVPE_EINVAL, "belief_step: ori and post overlap");
+  return CCVPE_OK;
+}
+
+// Launch two: ~1024 workgroups scale the maps; each merges the track's records first
+static int bf_finish(const float* heat, const float* ori, float one_minus_a, float floor_m, const int* reset, float* post,
+                     double* scratch, double* rows, int batch, int h, int w, long long ntiles, hipStream_t st) {
+  const size_t n = (size_t)h * w;
+  int slices = (1024 + batch - 1) / batch;
+  slices = slices < 1 ? 1 : (slices > 64 ? 64 : slices);
+  const size_t per = (n + slices - 1) / slices;
+  const int slice_len = (int)((per + 3) & ~(size_t)3);
+  slices = (int)((n + slice_len - 1) / slice_len);
+  if ((long long)slices * batch > 0x7fffffffLL) return fail(CCVPE_EINVAL, "belief_step: batch x slices > 2^31");
+  const bool vec2 = (n % 4) == 0 && aligned16(heat) && aligned16(post);
+  const dim3 grid2((unsigned)(slices * batch));
+  if (vec2)
+    hipLaunchKernelGGL(belief_finish_kernel<true>, grid2, dim3(256), 0, st, heat, ori, one_minus_a, floor_m, reset, post, scratch,
+                       rows, h, w, (int)ntiles, slices, slice_len);
+  else
+    hipLaunchKernelGGL(belief_finish_kernel<false>, grid2, dim3(256), 0, st, heat, ori, one_minus_a, floor_m, reset, post, scratch,
+                       rows, h, w, (int)ntiles, slices, slice_len);
+  return check_launch("belief_finish_kernel");
+}
+
+}  // namespace ccvpe
+
+extern "C" int ccvpe_belief_step_f32(const float* prior, const float* heat, const float* ori, const int* offsets,
+                                     const float* taps, int radius, float outlier, const int* reset, float* post,
+                                     double* scratch, double* rows, int batch, int h, int w, void* stream) {
+  int ntx, nty;
+  if (int rc = bf_check(prior, heat, ori, offsets, taps, radius, outlier, reset, post, scratch, rows, batch, h, w, &ntx, &nty))
+    return rc;
+  const long long ntiles = (long long)ntx * nty;
+  const size_t n = (size_t)h * w;
   hipStream_t st = (hipStream_t)stream;
   const float one_minus_a = 1.0f - outlier, floor_m = outlier / (float)n;
   const int smem = (int)sizeof(float) * (BF_TH + 2 * radius) * (bf_pitch(radius) + BF_TW);      // 64 000 B at R = 32
@@ -371,20 +490,25 @@ extern "C" int ccvpe_belief_step_f32(const float* prior, const float* heat, cons
                        scratch, h, w, ntx, nty);
   }
   if (int rc = check_launch("belief_predict_kernel")) return rc;
-  // ~1024 workgroups scale the maps; each merges the track's records first
-  int slices = (1024 + batch - 1) / batch;
-  slices = slices < 1 ? 1 : (slices > 64 ? 64 : slices);
-  const size_t per = (n + slices - 1) / slices;
-  const int slice_len = (int)((per + 3) & ~(size_t)3);
-  slices = (int)((n + slice_len - 1) / slice_len);
-  if ((long long)slices * batch > 0x7fffffffLL) return fail(CCVPE_EINVAL, "belief_step: batch x slices > 2^31");
-  const bool vec2 = (n % 4) == 0 && aligned16(heat) && aligned16(post);
-  const dim3 grid2((unsigned)(slices * batch));
-  if (vec2)
-    hipLaunchKernelGGL(belief_finish_kernel<true>, grid2, dim3(256), 0, st, heat, ori, one_minus_a, floor_m, reset, post, scratch,
-                       rows, h, w, (int)ntiles, slices, slice_len);
-  else
-    hipLaunchKernelGGL(belief_finish_kernel<false>, grid2, dim3(256), 0, st, heat, ori, one_minus_a, floor_m, reset, post, scratch,
-                       rows, h, w, (int)ntiles, slices, slice_len);
-  return check_launch("belief_finish_kernel");
+  return bf_finish(heat, ori, one_minus_a, floor_m, reset, post, scratch, rows, batch, h, w, ntiles, st);
+}
+
+extern "C" int ccvpe_belief_step_rigid_f32(const float* prior, const float* heat, const float* ori, const double* motion,
+                                           const float* taps, int radius, float outlier, const int* reset, float* post,
+                                           double* scratch, double* rows, int batch, int h, int w, void* stream) {
+  int ntx, nty;
+  if (int rc = bf_check(prior, heat, ori, motion, taps, radius, outlier, reset, post, scratch, rows, batch, h, w, &ntx, &nty))
+    return rc;
+  if (reinterpret_cast<uintptr_t>(motion) & 7) return fail(CCVPE_EINVAL, "belief_step_rigid: motion must be 8-byte aligned");
+  const long long ntiles = (long long)ntx * nty;
+  hipStream_t st = (hipStream_t)stream;
+  const float one_minus_a = 1.0f - outlier, floor_m = outlier / (float)((size_t)h * w);
+  const int smem = (int)sizeof(float) * (BF_TH + 2 * radius) * (bf_pitch(radius) + BF_TW);
+  auto kern = belief_predict_rigid_kernel;
+  static DevCache lds_set;
+  if (int rc = ensure_dyn_lds(lds_set, kern, smem, "belief_step_rigid")) return rc;
+  hipLaunchKernelGGL(kern, dim3((unsigned)(ntiles * batch)), dim3(256), smem, st, prior, heat, motion, taps, radius, one_minus_a,
+                     floor_m, reset, post, scratch, h, w, ntx, nty);
+  if (int rc = check_launch("belief_predict_rigid_kernel")) return rc;
+  return bf_finish(heat, ori, one_minus_a, floor_m, reset, post, scratch, rows, batch, h, w, ntiles, st);
 }

@@ -314,11 +314,13 @@ def evaluate_batches(forward_fn, batches, metres_per_pixel=None, sets=None):
     return res
 
 
-def evaluate_sequence(forward_fn, batches, filt, shift_px, starts, metres_per_pixel=None, sets=None):
+def evaluate_sequence(forward_fn, batches, filt, shift_px, starts, metres_per_pixel=None, sets=None, motion=None):
     """The reference's test protocol along a drive, for the raw heat-maps AND for the belief of a histogram filter
     (ccvpe_amd.tracking.HistogramFilter with one track).  `batches`: a DeviceBatches in drive order — unshuffled, one rank,
     targets=True (ValueError otherwise); shift_px [n,2] and starts [n] per sample of `batches.indices`, e.g. from
-    tracking.oxford_shifts(batches.pairs, batches.indices).  Per batch one forward and one ccvpe_eval_metrics_f32 launch for
+    tracking.oxford_shifts(batches.pairs, batches.indices).  motion [n,6] (tracking.kitti_motions(batches.pairs,
+    batches.indices): KITTI's patch frame turns between frames): every frame then steps with its motion row through the
+    rigid step and shift_px may be None.  Per batch one forward and one ccvpe_eval_metrics_f32 launch for
     the raw maps; then per frame one `filt.step` (reset first where starts says so) and one ccvpe_eval_metrics_f32 launch on the
     belief, all into device tables; ONE read-back after the loop.
     Returns {"raw": summarise(...), "filtered": summarise(...), "tracks": [n,14] (tracking.PRED_Y ... SURVIVED),
@@ -337,13 +339,22 @@ def evaluate_sequence(forward_fn, batches, filt, shift_px, starts, metres_per_pi
         raise ValueError("evaluate_sequence steps one track: HistogramFilter(1, ...)")
     starts = np.asarray(starts).reshape(-1).astype(bool)
     n = len(idx)
-    if len(starts) != n or len(shift_px) != n:
+    if motion is not None:
+        motion = np.asarray(motion, dtype=np.float64)
+        if len(starts) != n or motion.shape != (n, 6):
+            raise ValueError("evaluate_sequence: motion must be [%d,6] and starts hold one entry per sample of batches.indices" % n)
+    elif shift_px is None:
+        raise ValueError("evaluate_sequence: pass shift_px [n,2], or motion [n,6] for a patch frame that turns")
+    elif len(starts) != n or len(shift_px) != n:
         raise ValueError("evaluate_sequence: shift_px and starts must hold one entry per sample of batches.indices (%d)" % n)
     mpp = default_metres_per_pixel(batches.pairs) if metres_per_pixel is None else metres_per_pixel
     if sets is None:
         sets = default_sets(batches.pairs)
     dev = batches.device
-    shifts = torch.as_tensor(np.asarray(shift_px, dtype=np.float64).reshape(n, 2)).to(dev)
+    if motion is not None:
+        motions = torch.as_tensor(motion).to(dev)
+    else:
+        shifts = torch.as_tensor(np.asarray(shift_px, dtype=np.float64).reshape(n, 2)).to(dev)
     raw, fil, trk = (torch.empty((n, c), device=dev, dtype=torch.float64) for c in (12, 12, 14))
     if not isinstance(mpp, dict):
         mpp_const = torch.full((max(1, batches.batch_size),), float(mpp), device=dev, dtype=torch.float64)
@@ -359,7 +370,10 @@ def evaluate_sequence(forward_fn, batches, filt, shift_px, starts, metres_per_pi
         for j in range(b):
             if starts[k + j]:
                 filt.reset()
-            filt.step(heat[j:j + 1], ori[j:j + 1], shifts[k + j:k + j + 1], rows_out=trk[k + j:k + j + 1])
+            if motion is not None:
+                filt.step(heat[j:j + 1], ori[j:j + 1], motion=motions[k + j:k + j + 1], rows_out=trk[k + j:k + j + 1])
+            else:
+                filt.step(heat[j:j + 1], ori[j:j + 1], shifts[k + j:k + j + 1], rows_out=trk[k + j:k + j + 1])
             ops.eval_metrics(filt.belief, ori[j:j + 1], batch.gt[j:j + 1], batch.gt_ori[j:j + 1], batch.heading_deg[j:j + 1],
                              m[j:j + 1], out=fil[k + j:k + j + 1])
         k += b

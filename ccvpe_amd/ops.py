@@ -975,41 +975,55 @@ def belief_step(prior, heatmap, ori, offsets, taps, outlier=0.0, reset=None, pos
     (a non-zero entry starts that track from the measurement; its prior is not read).  post: a caller's [B,1,h,w] tensor that
     does not overlap prior; scratch: B * belief_partials(h, w) float64; out: a caller's [B,14] float64 slice of a larger table.
     Returns (rows [B,14] float64 — columns ccvpe_amd.tracking.PRED_Y ... SURVIVED, post)."""
+    return _belief_step("belief_step", "ccvpe_belief_step_f32", prior, heatmap, ori, offsets, "offsets", torch.int32, 2, taps,
+                        outlier, reset, post, scratch, out)
+
+
+def belief_step_rigid(prior, heatmap, ori, motion, taps, outlier=0.0, reset=None, post=None, scratch=None, out=None):
+    """belief_step with the predict replaced by a rigid motion of the grid (ccvpe_amd.tracking.step_rigid_spec is the
+    specification): the prior resampled bilinearly through `motion` [B,6] float64 on the device — rows (a00, a01, a02, a10, a11,
+    a12) of the INVERSE map, output pixel (y, x) reads the prior at ((a00 y + a01 x) + a02, (a10 y + a11 x) + a12), as
+    tracking.rigid_motion and tracking.kitti_motions return them — then blurred by `taps` [B,2,2R+1] (centred:
+    tracking.motion_taps(zeros, sigma, R)).  Every other argument, every check and the return value are belief_step's."""
+    return _belief_step("belief_step_rigid", "ccvpe_belief_step_rigid_f32", prior, heatmap, ori, motion, "motion", torch.float64, 6,
+                        taps, outlier, reset, post, scratch, out)
+
+
+def _belief_step(who, entry, prior, heatmap, ori, move, move_name, move_dtype, move_cols, taps, outlier, reset, post, scratch, out):
     lib = _lib.load()
     for t, nm in ((prior, "prior"), (heatmap, "heatmap"), (ori, "ori"), (taps, "taps"), (post, "post")):
         _chk(t, nm)
-    for t, nm in ((offsets, "offsets"), (reset, "reset")):
-        _chk(t, nm, torch.int32)
+    _chk(move, move_name, move_dtype)
+    _chk(reset, "reset", torch.int32)
     for t, nm in ((scratch, "scratch"), (out, "out")):
         _chk(t, nm, torch.float64)
     if heatmap.dim() != 4 or heatmap.shape[1] != 1:
-        raise ValueError("belief_step: heatmap [B,1,h,w] expected, got %s" % (tuple(heatmap.shape),))
+        raise ValueError("%s: heatmap [B,1,h,w] expected, got %s" % (who, tuple(heatmap.shape)))
     b, _, h, w = heatmap.shape
     if prior.shape != heatmap.shape or ori.shape != (b, 2, h, w):
-        raise ValueError("belief_step: prior [B,1,h,w] like heatmap and ori [B,2,h,w] expected")
+        raise ValueError("%s: prior [B,1,h,w] like heatmap and ori [B,2,h,w] expected" % who)
     if taps.dim() != 3 or taps.shape[0] != b or taps.shape[1] != 2 or taps.shape[2] % 2 != 1:
-        raise ValueError("belief_step: taps must be [%d,2,2R+1], got %s" % (b, tuple(taps.shape)))
+        raise ValueError("%s: taps must be [%d,2,2R+1], got %s" % (who, b, tuple(taps.shape)))
     radius = (taps.shape[2] - 1) // 2
-    if tuple(offsets.shape) != (b, 2):
-        raise ValueError("belief_step: offsets must be [%d,2], got %s" % (b, tuple(offsets.shape)))
+    if tuple(move.shape) != (b, move_cols):
+        raise ValueError("%s: %s must be [%d,%d], got %s" % (who, move_name, b, move_cols, tuple(move.shape)))
     if reset is not None and reset.numel() != b:
-        raise ValueError("belief_step: reset must hold one flag per track")
+        raise ValueError("%s: reset must hold one flag per track" % who)
     need = b * belief_partials(h, w)
     if scratch is None:
         scratch = _empty((need,), device=heatmap.device, dtype=torch.float64)
     elif scratch.numel() < need:
-        raise ValueError("belief_step: scratch holds %d doubles, %d needed" % (scratch.numel(), need))
+        raise ValueError("%s: scratch holds %d doubles, %d needed" % (who, scratch.numel(), need))
     if post is None:
         post = _empty(tuple(heatmap.shape), device=heatmap.device)
     elif post.shape != heatmap.shape:
-        raise ValueError("belief_step: post must be %s, got %s" % (tuple(heatmap.shape), tuple(post.shape)))
+        raise ValueError("%s: post must be %s, got %s" % (who, tuple(heatmap.shape), tuple(post.shape)))
     if out is None:
         out = _empty((b, 14), device=heatmap.device, dtype=torch.float64)
     elif tuple(out.shape) != (b, 14):
-        raise ValueError("belief_step: out must be [%d,14], got %s" % (b, tuple(out.shape)))
-    check(lib.ccvpe_belief_step_f32(_ptr(prior), _ptr(heatmap), _ptr(ori), _ptr(offsets), _ptr(taps), radius, float(outlier),
-                                    _ptr(reset), _ptr(post), _ptr(scratch), _ptr(out), b, h, w, _stream()),
-          "ccvpe_belief_step_f32")
+        raise ValueError("%s: out must be [%d,14], got %s" % (who, b, tuple(out.shape)))
+    check(getattr(lib, entry)(_ptr(prior), _ptr(heatmap), _ptr(ori), _ptr(move), _ptr(taps), radius, float(outlier),
+                              _ptr(reset), _ptr(post), _ptr(scratch), _ptr(out), b, h, w, _stream()), entry)
     return out, post
 
 

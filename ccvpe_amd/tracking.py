@@ -14,10 +14,16 @@ launches (csrc/belief.hip); `HistogramFilter` owns the belief buffers of a set o
 and a noise level into the integer offset and the blur taps; `oxford_shifts` derives the per-frame shifts of an Oxford
 traversal; `evaluate.evaluate_sequence` reports the reference's protocol numbers for the raw and the filtered estimate.
 
-Out of scope: rotation between patch frames (the grid only translates), KITTI's randomly rotated test patches, learned
-motion models, bf16 beliefs.
+Where the patch frame also turns between two frames (KITTI: every aerial patch is re-centred on the vehicle, turned to its
+heading and rotated by the sample's theta) the predict is a rigid motion: the prior is resampled bilinearly through the inverse
+map of `rigid_motion` and then blurred with centred taps — `step_rigid_spec` is the specification, `ops.belief_step_rigid` the
+device step, `HistogramFilter.step(motion=...)` the filter's entry and `kitti_motions` the per-frame motions of a KITTI test
+split.
+
+Out of scope: a change of scale between patch frames, learned motion models, bf16 beliefs.
 """
 import math
+import os
 
 import numpy as np
 import torch
@@ -79,6 +85,13 @@ def _predict_spec(prior, oy, ox, ky, kx):
     vy, vx = (ys >= 0) & (ys < h), (xs >= 0) & (xs < w)
     if vy.any() and vx.any():
         pad[np.ix_(vy, vx)] = prior[np.ix_(ys[vy], xs[vx])]
+    return _blur_spec(pad, ky, kx)
+
+
+def _blur_spec(pad, ky, kx):
+    """The separable blur of a moved prior that carries its R halo: [h + 2R, w + 2R] -> [h, w], rows then columns."""
+    r = (len(ky) - 1) // 2
+    h, w = pad.shape[0] - 2 * r, pad.shape[1] - 2 * r
     row = np.zeros((h + 2 * r, w), dtype=np.float64)
     for j in range(-r, r + 1):
         row += np.float64(kx[j + r]) * pad[:, r - j:r - j + w]
@@ -107,12 +120,94 @@ def step_spec(prior, heat, ori, offsets, taps, outlier=0.0, reset=None, return_u
     Row: first maximum of U (PRED_Y, PRED_X), post there (PROB), ori there (COS, SIN) and its angle (ANGLE), Z (EVIDENCE),
     RESET, the mean and covariance of U / Z over integer pixel coordinates (MEAN_Y, MEAN_X, VAR_YY, VAR_XX, COV_YX), S
     (SURVIVED).  Returns (post float32 [B,h,w], rows float64 [B,14]) and, with return_u, U float64 [B,h,w]."""
+    b = np.asarray(heat).shape[0]
+    offsets = np.asarray(offsets).reshape(b, 2)
+    return _step_spec(prior, heat, ori, lambda t, p, ky, kx: _predict_spec(p, offsets[t, 0], offsets[t, 1], ky, kx), taps,
+                      outlier, reset, return_u)
+
+
+def rigid_motion(shift_px, angle_deg, hw, centre=None):
+    """The inverse map of a rigid motion of the grid, [B,6] float64 rows (a00, a01, a02, a10, a11, a12): output pixel (y, x)
+    takes its value from the previous belief at
+
+        sy = (a00 y + a01 x) + a02,   sx = (a10 y + a11 x) + a12.
+
+    The forward motion is q = c + Rot(angle)(p - c) + shift with shift = (dy, dx) and c = `centre` (y, x), by default the grid
+    centre ((h-1)/2, (w-1)/2).  A positive angle turns counter-clockwise as seen in the image (x right, y down) — the sense of
+    Pillow's `rotate` and of the KITTI loader's `ori`: a point 10 px right of the centre lands 10 px above it at 90 degrees.
+    The angle is reduced to a quarter turn plus a remainder in [-45, 45] before sin / cos, so multiples of 90 degrees give
+    exact 0 / +-1 entries.  shift_px [B,2] (or one pair), angle_deg [B] (or one value), centre [B,2] or one pair."""
+    s = np.asarray(shift_px, dtype=np.float64).reshape(-1, 2)
+    ang = np.asarray(angle_deg, dtype=np.float64).reshape(-1)
+    n = max(s.shape[0], ang.shape[0])
+    s, ang = np.broadcast_to(s, (n, 2)), np.broadcast_to(ang, (n,))
+    c = np.asarray(((hw[0] - 1) / 2.0, (hw[1] - 1) / 2.0) if centre is None else centre, dtype=np.float64).reshape(-1, 2)
+    c = np.broadcast_to(c, (n, 2))
+    out = np.zeros((n, 6), dtype=np.float64)
+    for t in range(n):
+        a = math.fmod(float(ang[t]), 360.0) if math.isfinite(float(ang[t])) else float("nan")
+        if a != a:
+            out[t] = np.nan
+            continue
+        k = int(math.floor(a / 90.0 + 0.5))
+        rem = math.radians(a - 90.0 * k)
+        cr, sr = math.cos(rem), math.sin(rem)                                  # rem = 0 gives exactly (1, 0)
+        co, si = ((cr, sr), (-sr, cr), (-cr, -sr), (sr, -cr))[k % 4]            # cos, sin of 90 k + rem
+        # forward in (y, x): q - c - shift = [[co, -si], [si, co]] (p - c); the inverse is the transpose
+        ty, tx = c[t, 0] + s[t, 0], c[t, 1] + s[t, 1]
+        out[t] = (co, si, c[t, 0] - (co * ty + si * tx), -si, co, c[t, 1] - (-si * ty + co * tx))
+    return out
+
+
+def _warp_spec(prior, m, r):
+    """W on the grid extended by the blur's halo, [h + 2R, w + 2R]: the bilinear sample of the prior (0 outside its grid) at
+    (sy, sx) of every pixel y in [-R, h + R), x in [-R, w + R); weights cast to fp32, combines in float64."""
+    h, w = prior.shape
+    ys = np.arange(-r, h + r, dtype=np.float64).reshape(-1, 1)
+    xs = np.arange(-r, w + r, dtype=np.float64).reshape(1, -1)
+    with np.errstate(invalid="ignore", over="ignore"):
+        sy = (m[0] * ys + m[1] * xs) + m[2]
+        sx = (m[3] * ys + m[4] * xs) + m[5]
+        ok = np.isfinite(sy) & np.isfinite(sx) & (sy > -1) & (sy < h) & (sx > -1) & (sx < w)
+    sy, sx = np.where(ok, sy, 0.0), np.where(ok, sx, 0.0)
+    fy0, fx0 = np.floor(sy), np.floor(sx)
+    fy, fx = sy - fy0, sx - fx0
+    wy1, wy0 = fy.astype(np.float32).astype(np.float64), (1 - fy).astype(np.float32).astype(np.float64)
+    wx1, wx0 = fx.astype(np.float32).astype(np.float64), (1 - fx).astype(np.float32).astype(np.float64)
+    pad = np.zeros((h + 2, w + 2), dtype=np.float64)                            # index + 1: taps at -1 and at h, w are 0
+    pad[1:-1, 1:-1] = prior
+    iy, ix = fy0.astype(np.int64) + 1, fx0.astype(np.int64) + 1
+    top = wx0 * pad[iy, ix] + wx1 * pad[iy, ix + 1]
+    bot = wx0 * pad[iy + 1, ix] + wx1 * pad[iy + 1, ix + 1]
+    return np.where(ok, wy0 * top + wy1 * bot, 0.0)
+
+
+def step_rigid_spec(prior, heat, ori, motion, taps, outlier=0.0, reset=None, return_u=False):
+    """The specification of ccvpe_belief_step_rigid_f32: `step_spec` with the predict replaced by a warp and the same blur.
+    motion [B,6] float64, the inverse map as `rigid_motion` returns it (any values, NaN and inf included):
+
+        W[y,x] = bilinear sample of the prior at (sy, sx) = ((a00 y + a01 x) + a02, (a10 y + a11 x) + a12), prior = 0 outside
+                 the grid: y0 = floor(sy), fy = sy - y0, wy1 = float32(fy), wy0 = float32(1 - fy), wx1, wx0 likewise,
+                 top = wx0 v00 + wx1 v01, bot = wx0 v10 + wx1 v11, W = wy0 top + wy1 bot; 0 where (sy, sx) is not finite or
+                 not in (-1, h) x (-1, w)
+        Q      = the separable blur of W with `taps` (W is taken on the grid plus its R halo, not cropped before the blur)
+
+    and everything after that — measure, reset rules, the 14 columns, SURVIVED = sum Q — as step_spec.  Sub-pixel shifts live
+    in the warp, so callers pass centred taps: motion_taps(zeros, sigma, R).  For angle 0 and a FRACTIONAL shift this is not
+    the translate path's result: here the prior is resampled bilinearly, there the Gaussian taps themselves are shifted (for
+    angle 0 and integer shifts the two are equal, value for value)."""
+    b = np.asarray(heat).shape[0]
+    motion = np.asarray(motion, dtype=np.float64).reshape(b, 6)
+    return _step_spec(prior, heat, ori, lambda t, p, ky, kx: _blur_spec(_warp_spec(p, motion[t], (len(ky) - 1) // 2), ky, kx),
+                      taps, outlier, reset, return_u)
+
+
+def _step_spec(prior, heat, ori, predict, taps, outlier, reset, return_u):
     heat = np.asarray(heat, dtype=np.float32)
     b, h, w = heat.shape[0], heat.shape[-2], heat.shape[-1]
     heat = heat.reshape(b, h, w).astype(np.float64)
     prior = np.asarray(prior, dtype=np.float32).reshape(b, h, w).astype(np.float64)
     ori = np.asarray(ori, dtype=np.float32).reshape(b, 2, h, w)
-    offsets = np.asarray(offsets).reshape(b, 2)
     taps = np.asarray(taps, dtype=np.float32).reshape(b, 2, -1)
     alpha = np.float64(np.float32(outlier))
     post = np.zeros((b, h, w), dtype=np.float32)
@@ -125,7 +220,7 @@ def step_spec(prior, heat, ori, offsets, taps, outlier=0.0, reset=None, return_u
         if reset is not None and int(np.asarray(reset).reshape(-1)[t]) != 0:
             state = 1
         else:
-            q = _predict_spec(prior[t], offsets[t, 0], offsets[t, 1], taps[t, 0], taps[t, 1])
+            q = predict(t, prior[t], taps[t, 0], taps[t, 1])
             u = q * m
             z, survived = float(u.sum()), float(q.sum())
             if not (z > 0 and np.isfinite(z)):
@@ -177,6 +272,7 @@ class HistogramFilter(object):
         self._scratch = torch.empty((self.n_tracks * ops.belief_partials(h, w),), device=self.device, dtype=torch.float64)
         self.rows = torch.zeros((self.n_tracks, 14), device=self.device, dtype=torch.float64)
         self._reset = torch.ones((self.n_tracks,), device=self.device, dtype=torch.int32)
+        self._zero_shift = None                                                 # step(motion=...): centred taps
 
     @property
     def belief(self):
@@ -191,14 +287,33 @@ class HistogramFilter(object):
         else:
             self._reset[tracks] = 1
 
-    def step(self, heatmap, ori, shift_px, sigma_px=None, rows_out=None):
-        """One filter step: heatmap [B,1,h,w], ori [B,2,h,w] from the forward; shift_px [B,2] = (dy, dx), the motion of the
-        vehicle in the grid since the previous step (odometry minus the motion of the aerial patch), a tensor on any device or
-        an array.  Returns the rows [B,14] (columns PRED_Y ... SURVIVED): `rows_out` when given (a slice of a caller's table),
-        else self.rows, which the next step overwrites."""
+    def step(self, heatmap, ori, shift_px=None, sigma_px=None, rows_out=None, motion=None):
+        """One filter step: heatmap [B,1,h,w], ori [B,2,h,w] from the forward, and exactly one of (ValueError otherwise)
+        shift_px [B,2] = (dy, dx), the motion of the vehicle in the grid since the previous step (odometry minus the motion of
+        the aerial patch), or motion [B,6] float64, the inverse map of a rigid motion of the grid (`rigid_motion`,
+        `kitti_motions`): the belief is then resampled through it and blurred with centred taps (ops.belief_step_rigid).
+        Both are tensors on any device or arrays.  Returns the rows [B,14] (columns PRED_Y ... SURVIVED): `rows_out` when given
+        (a slice of a caller's table), else self.rows, which the next step overwrites."""
         from . import ops
+        if (shift_px is None) == (motion is None):
+            raise ValueError("step: pass exactly one of shift_px and motion")
         if tuple(heatmap.shape) != (self.n_tracks, 1) + self.hw:
             raise ValueError("step: heatmap must be %s, got %s" % ((self.n_tracks, 1) + self.hw, tuple(heatmap.shape)))
+        if motion is not None:
+            mot = motion if torch.is_tensor(motion) else torch.from_numpy(np.array(motion, dtype=np.float64))      # a copy
+            mot = mot.to(device=self.device, dtype=torch.float64)
+            if mot.numel() != 6 * self.n_tracks:
+                raise ValueError("step: motion must be [%d,6]" % self.n_tracks)
+            mot = mot.reshape(self.n_tracks, 6).contiguous()
+            if self._zero_shift is None:
+                self._zero_shift = torch.zeros((self.n_tracks, 2), device=self.device, dtype=torch.float64)
+            _, taps = motion_taps(self._zero_shift, self.sigma_px if sigma_px is None else sigma_px, self.radius)
+            rows = self.rows if rows_out is None else rows_out
+            ops.belief_step_rigid(self._buf[self._cur], heatmap, ori, mot, taps, outlier=self.outlier, reset=self._reset,
+                                  post=self._buf[1 - self._cur], scratch=self._scratch, out=rows)
+            self._reset.zero_()
+            self._cur = 1 - self._cur
+            return rows
         shift = torch.as_tensor(shift_px).to(self.device)
         if shift.numel() != 2 * self.n_tracks:
             raise ValueError("step: shift_px must be [%d,2]" % self.n_tracks)
@@ -244,3 +359,98 @@ def oxford_shifts(pairs, indices=None):
             shift[n, 1] = 512.0 / 800.0 * ((cur[1] - prev[1]) - (cur[3] - prev[3]))
         prev = cur
     return shift, starts
+
+
+EARTH_RADIUS_M = 6378137.0                  # WGS-84 equatorial radius: the local tangent plane of kitti_motions
+
+
+def _rot2(rad):
+    c, s = math.cos(rad), math.sin(rad)
+    return np.array([[c, -s], [s, c]], dtype=np.float64)
+
+
+def _kitti_frame(pairs, i):
+    """What places the patch of test sample i in the world: (name, lat, lon, heading [rad], ori [deg], shift, cam) with
+    shift and cam in map pixels, x east / y UP after the heading turn (the loader's image offsets with y flipped)."""
+    from . import datasets
+    name = pairs.lines[i].split(" ")[0]
+    with open(pairs.paths(name)[1]) as f:
+        rec = f.readline().split(" ")
+    sx, sy, ori = pairs.perturbation(i)
+    mpp = pairs.meter_per_pixel
+    shift = np.array([sx * pairs.shift_px_lon, sy * pairs.shift_px_lat])
+    cam = np.array([datasets.KITTI_CAMERA_SHIFT[0] / mpp, -datasets.KITTI_CAMERA_SHIFT[1] / mpp])
+    return name, float(rec[0]), float(rec[1]), float(rec[5]), float(ori), shift, cam
+
+
+def _kitti_pair_motion(pairs, prev, cur, with_camera):
+    """The motion from the patch of frame `prev` to the patch of frame `cur` (outputs of _kitti_frame) as a rigid_motion row.
+    Patch frame t relates to the world by the loader's chain (KITTIPairs.sample: rotate(-heading), the camera offset, the
+    shift, rotate(ori), centre crop), in map pixels with y up and p measured from the patch centre:
+
+        F_t(p) = G_t + Rot(heading_t) [ Rot(-ori_t) p + shift_t + cam ]
+
+    G_t is the map centre = the GPS antenna, from latitude and longitude on a local tangent plane.  with_camera adds the
+    camera's own displacement dC = (G_t - G_{t-1}) + (Rot(heading_t) - Rot(heading_{t-1})) cam to the world point."""
+    _, lat0, lon0, h0, o0, s0, cam = prev
+    _, lat1, lon1, h1, o1, s1, _ = cur
+    mpp = pairs.meter_per_pixel
+    mid = math.radians(0.5 * (lat0 + lat1))
+    dg = np.array([EARTH_RADIUS_M * math.cos(mid) * math.radians(lon1 - lon0), EARTH_RADIUS_M * math.radians(lat1 - lat0)]) / mpp
+    world = -dg                                                                  # G_{t-1} - G_t
+    if with_camera:
+        world = world + (dg + (_rot2(h1) - _rot2(h0)) @ cam)
+    r_out = _rot2(math.radians(o1))
+    # the image of the patch centre, and the total turn; in the image (y down) the shift is (dy, dx) = (-T_y, T_x)
+    t = r_out @ (_rot2(-h1) @ (world + _rot2(h0) @ (s0 + cam)) - s1 - cam)
+    angle = (o1 - o0) + math.degrees(h0 - h1)
+    from . import datasets
+    return rigid_motion([-t[1], t[0]], angle, (datasets.KITTI_CROP, datasets.KITTI_CROP))[0]
+
+
+def _need_kitti_test(pairs, who):
+    if not getattr(pairs, "test", False) or not hasattr(pairs, "perturbation"):
+        raise ValueError("%s needs a KITTIPairs(test=True) split (training perturbations are random draws)" % who)
+
+
+def kitti_frame_motion(pairs, i_prev, i_cur):
+    """The change of the PATCH FRAME alone between two samples of a KITTIPairs(test=True) split, as a rigid_motion row
+    [6]: a world-fixed point seen at p in the patch of sample i_prev is seen at q in the patch of sample i_cur, and the row
+    maps q back to p (F_cur^-1 o F_prev in the notation of kitti_motions)."""
+    _need_kitti_test(pairs, "kitti_frame_motion")
+    return _kitti_pair_motion(pairs, _kitti_frame(pairs, int(i_prev)), _kitti_frame(pairs, int(i_cur)), False)
+
+
+def kitti_motions(pairs, indices=None):
+    """Per-frame rigid motions of a KITTI test split: (motion float64 [n,6] as `rigid_motion` rows, starts bool [n]).
+
+    Every KITTI aerial patch is re-centred on the vehicle, turned so that the heading points east, shifted and rotated by the
+    sample's theta, so the belief of frame t-1 reaches the grid of frame t through a rotation plus a translation:
+
+        motion_t = F_t^-1 o (F_{t-1} + dC),      F_t(p) = G_t + mpp Rot(heading_t) [ Rot(-ori_t) p + shift_t + cam ]
+
+    (image y flipped; see _kitti_pair_motion) where dC is the camera's world displacement: the OXTS latitude and longitude
+    (fields 0 and 1) on a local tangent plane with R = 6 378 137 m, converted to map pixels with the loader's metres per pixel,
+    plus the antenna-to-camera lever arm under the heading change.  `starts` marks the first index, a change of drive
+    (name[:38]) and a frame number that is not greater than its predecessor's; a start carries the identity motion and is
+    where a filter must be reset.  A training split raises ValueError: its perturbations are random draws.
+
+    NOTE: this uses the GROUND-TRUTH pose difference as the odometry — the OXTS record is what the data set's ground truth is
+    made of.  It shows what the filter does with good odometry; it is not a fair comparison against single-frame results."""
+    _need_kitti_test(pairs, "kitti_motions")
+    idx = np.arange(len(pairs)) if indices is None else np.asarray(indices, dtype=np.int64)
+    motion = np.tile(np.array([1.0, 0.0, 0.0, 0.0, 1.0, 0.0]), (len(idx), 1))
+    starts = np.zeros((len(idx),), dtype=bool)
+    prev = None
+    for n, i in enumerate(idx):
+        cur = _kitti_frame(pairs, int(i))
+        if n == 0 or cur[0][:38] != prev[0][:38] or _kitti_frame_number(cur[0]) <= _kitti_frame_number(prev[0]):
+            starts[n] = True
+        else:
+            motion[n] = _kitti_pair_motion(pairs, prev, cur, True)
+        prev = cur
+    return motion, starts
+
+
+def _kitti_frame_number(name):
+    return int(os.path.splitext(name[38:])[0])

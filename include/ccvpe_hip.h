@@ -496,11 +496,26 @@ int ccvpe_eval_metrics_f32(const float* heatmap, const float* ori, const float* 
  * bad shape); rows [B,14] doubles — any rows of a larger table; rows and scratch 8-byte aligned.  16-byte loads of the prior
  * when w % 4 == 0 and it is 16-byte aligned, of heat / post when h*w % 4 == 0 and they are.  Non-finite inputs: the call
  * returns, reset is 2 and the rest of the row is unspecified.
+ *
+ * ccvpe_belief_step_rigid_f32 (specification: tracking.step_rigid_spec): the same step with the predict replaced by a rigid
+ * motion of the grid — a warp, then the same blur.  motion [B,6] doubles (a00, a01, a02, a10, a11, a12), the INVERSE map
+ * (tracking.rigid_motion), 8-byte aligned, any values:
+ *   warp     W[y,x] = bilinear sample of the prior (0 outside the grid) at sy = (a00 y + a01 x) + a02, sx = (a10 y + a11 x)
+ *            + a12, each product and sum rounded to double in that order; y0 = floor(sy), weights (float)(sy - y0) and
+ *            (float)(1 - (sy - y0)), likewise in x; top = wx0 v00 + wx1 v01, bot = wx0 v10 + wx1 v11, W = wy0 top + wy1 bot
+ *            in fp32 (a product, then one fma); 0 where (sy, sx) is not finite or not in (-1, h) x (-1, w)
+ *   predict  Q = the separable blur of W with taps (centred taps: sub-pixel shifts live in the warp); W is taken on the grid
+ *            plus the blur's halo, not cropped before the blur
+ * Every other argument, the scratch size, the rows and the reset rules are those of ccvpe_belief_step_f32; for a00 = a11 = 1,
+ * a01 = a10 = 0 and integer a02 = -oy, a12 = -ox the two give the same bits.  Same launches: two, no floating-point atomics.
  * ----------------------------------------------------------------------------------------- */
 int ccvpe_belief_partials(int h, int w);
 int ccvpe_belief_step_f32(const float* prior, const float* heat, const float* ori, const int* offsets, const float* taps,
                           int radius, float outlier, const int* reset, float* post, double* scratch, double* rows,
                           int batch, int h, int w, void* stream);
+int ccvpe_belief_step_rigid_f32(const float* prior, const float* heat, const float* ori, const double* motion,
+                                const float* taps, int radius, float outlier, const int* reset, float* post, double* scratch,
+                                double* rows, int batch, int h, int w, void* stream);
 
 /* -------------------------------------------------------------------------------------------
  * Losses (losses.py:4-29), device scalars out.  `acc` is caller-provided scratch.
