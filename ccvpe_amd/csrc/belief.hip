@@ -13,6 +13,16 @@
 // The rigid step (ccvpe_belief_step_rigid_f32; tracking.step_rigid_spec) replaces only the staging of launch one:
 // belief_predict_rigid_kernel fills the LDS tile with the prior resampled bilinearly through the track's inverse motion map and
 // then runs the same passes (bf_blur_measure); launch two is the same kernel.
+//
+// The backward step of the forward-backward smoother (ccvpe_belief_smooth_step_f32 / _rigid_f32; tracking.smooth_step_spec /
+// smooth_step_rigid_spec) has the same two-launch shape and is built from the same pieces.  Launch one, belief_smooth_kernel /
+// belief_smooth_rigid_kernel: the staging helpers (bf_stage_shift, bf_stage_warp) form G = fma(1 - a, heat, floor) beta on the
+// way into LDS — the measurement enters BEFORE the blur — with the offsets added instead of subtracted (the rigid form walks
+// the inverted motion); bf_passes runs the row and column passes with the taps indexed in reverse, which together with the
+// sign is the adjoint of the predict; bf_epilogue multiplies with the stored posterior alpha, writes B' and V = alpha B' and
+// the forward record with alpha in M's place.  Launch two, belief_smooth_finish_kernel: the shared record merge
+// (bf_merge_records), the state, BOTH maps scaled (or the fallback written), the shared row (bf_write_row).
+// What is not shared: the value a staged pixel takes (bf_src), the second output map and the two-map scaling loop.
 #include "common.h"
 
 namespace ccvpe {
@@ -21,6 +31,7 @@ constexpr int BF_TH = 16, BF_TW = 64;         // output tile; 256 threads
 constexpr int BF_REC = 18;                     // doubles per workgroup record
 // record layout: [0] sum Q | [1..6] U: s, sy, sx, syy, sxx, syx | [7..12] the same of M | [13] max U [14] its index |
 //                [15] max M [16] its index | [17] unused
+// the backward step: [0] sum B' | [1..6] V | [7..12] alpha | max V | max alpha
 constexpr int BF_NSUM = 13;
 constexpr int BF_NONE = 0x7fffffff;
 
@@ -63,76 +74,67 @@ __device__ __forceinline__ void bf_moments(double* m, float v, int y, int x) {
   m[5] = fma(d * dy, dx, m[5]);
 }
 
-__device__ __forceinline__ void bf_blur_measure(const float* T, float* mid, const float* __restrict__ heat,
-                                                const float* __restrict__ taps, int R, float one_minus_a, float floor_m,
-                                                bool skip, float* __restrict__ post, double* __restrict__ scratch, int b,
-                                                int tile, int ntiles, int y0, int x0, int h, int w);
-
-template <bool VEC>
-__global__ __launch_bounds__(256) void belief_predict_kernel(const float* __restrict__ prior, const float* __restrict__ heat,
-                                                             const int* __restrict__ offsets, const float* __restrict__ taps,
-                                                             int R, float one_minus_a, float floor_m,
-                                                             const int* __restrict__ reset, float* __restrict__ post,
-                                                             double* __restrict__ scratch, int h, int w, int ntx, int nty) {
-  extern __shared__ cc_f32x4 bf_smem[];
-  const int tid = threadIdx.x;
-  const int ntiles = ntx * nty;
-  const int b = blockIdx.x / ntiles, tile = blockIdx.x - b * ntiles;
-  const int y0 = (tile / ntx) * BF_TH, x0 = (tile % ntx) * BF_TW;
-  const int rows = BF_TH + 2 * R, PW = bf_pitch(R);
-  float* T = reinterpret_cast<float*>(bf_smem);                  // [rows][PW]: T[r][c] = prior(y0 + r - R - oy, x0 + c - R - ox)
-  float* mid = T + rows * PW;                                    // [rows][BF_TW]: the row pass
-  const bool skip = reset != nullptr && reset[b] != 0;           // a reset track starts from the measurement: no predict
-  const size_t n = (size_t)h * w;
-  const float* pb = prior + (size_t)b * n;
-
-  if (!skip) {
-    // 64-bit coordinates: the offsets may be any int32
-    const long long oy = offsets[2 * b], ox = offsets[2 * b + 1];
-    const long long gy0 = (long long)y0 - R - oy, gx0 = (long long)x0 - R - ox;
-    if (VEC) {                                                   // w % 4 == 0 and a 16-byte aligned prior: aligned quads are
-      const long long gxa = gx0 & ~3LL;                          // wholly inside or wholly outside a row
-      const int lead = (int)(gx0 - gxa);
-      const int nq = (PW + lead + 3) >> 2;
-      for (int idx = tid; idx < rows * nq; idx += 256) {
-        const int r = idx / nq, q = idx - r * nq;
-        const long long gy = gy0 + r, gx = gxa + 4 * q;
-        cc_f32x4 v = {0.f, 0.f, 0.f, 0.f};
-        if (gy >= 0 && gy < h && gx >= 0 && gx < w) v = *reinterpret_cast<const cc_f32x4*>(pb + (size_t)gy * w + (size_t)gx);
-        const int c = 4 * q - lead;
-        if (lead == 0) {
-          *reinterpret_cast<cc_f32x4*>(T + r * PW + c) = v;      // q < PW / 4 here
-        } else {
-#pragma unroll
-          for (int e = 0; e < 4; ++e)
-            if (c + e >= 0 && c + e < PW) T[r * PW + c + e] = v[e];
-        }
-      }
-    } else {
-      for (int idx = tid; idx < rows * PW; idx += 256) {
-        const int r = idx / PW, c = idx - r * PW;
-        const long long gy = gy0 + r, gx = gx0 + c;
-        float v = 0.f;
-        if (gy >= 0 && gy < h && gx >= 0 && gx < w) v = pb[(size_t)gy * w + (size_t)gx];
-        T[idx] = v;
-      }
-    }
-  }
-  bf_blur_measure(T, mid, heat, taps, R, one_minus_a, floor_m, skip, post, scratch, b, tile, ntiles, y0, x0, h, w);
+// The value a staged pixel takes from global memory: the prior itself (the forward step), or the backward step's
+// G = M beta with M = fma(1 - a, heat, floor) formed on the way into LDS (v = heat, v2 = beta).
+template <bool SMOOTH>
+__device__ __forceinline__ float bf_src(float v, float v2, float one_minus_a, float floor_m) {
+  return SMOOTH ? __fmul_rn(fmaf(one_minus_a, v, floor_m), v2) : v;
 }
 
-// Everything after the staging of T (the moved prior of the tile with its R halo), for both predict kernels: the barrier, the
-// row pass, the column pass, the measure, U and the tile's record.
-__device__ __forceinline__ void bf_blur_measure(const float* T, float* mid, const float* __restrict__ heat,
-                                                const float* __restrict__ taps, int R, float one_minus_a, float floor_m,
-                                                bool skip, float* __restrict__ post, double* __restrict__ scratch, int b,
-                                                int tile, int ntiles, int y0, int x0, int h, int w) {
-  __shared__ double red[4][BF_NSUM];
-  __shared__ float rv[2][4];
-  __shared__ int ri[2][4];
+// Stage the tile plus its R halo of a map moved by whole pixels: T[r][c] = src(gy0 + r, gx0 + c), zero outside the grid.
+// 64-bit coordinates: the offsets may be any int32.  VEC: w % 4 == 0 and 16-byte aligned maps, so aligned quads are wholly
+// inside or wholly outside a row; the backward step loads two quads (heat, beta) per LDS quad.
+template <bool VEC, bool SMOOTH>
+__device__ __forceinline__ void bf_stage_shift(float* T, const float* __restrict__ pb, const float* __restrict__ pb2,
+                                               float one_minus_a, float floor_m, long long gy0, long long gx0, int rows, int PW,
+                                               int h, int w) {
+  const int tid = threadIdx.x;
+  if (VEC) {
+    const long long gxa = gx0 & ~3LL;
+    const int lead = (int)(gx0 - gxa);
+    const int nq = (PW + lead + 3) >> 2;
+    for (int idx = tid; idx < rows * nq; idx += 256) {
+      const int r = idx / nq, q = idx - r * nq;
+      const long long gy = gy0 + r, gx = gxa + 4 * q;
+      cc_f32x4 v = {0.f, 0.f, 0.f, 0.f};
+      if (gy >= 0 && gy < h && gx >= 0 && gx < w) {
+        v = *reinterpret_cast<const cc_f32x4*>(pb + (size_t)gy * w + (size_t)gx);
+        if (SMOOTH) {
+          const cc_f32x4 v2 = *reinterpret_cast<const cc_f32x4*>(pb2 + (size_t)gy * w + (size_t)gx);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) v[e] = bf_src<true>(v[e], v2[e], one_minus_a, floor_m);
+        }
+      }
+      const int c = 4 * q - lead;
+      if (lead == 0) {
+        *reinterpret_cast<cc_f32x4*>(T + r * PW + c) = v;        // q < PW / 4 here
+      } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+          if (c + e >= 0 && c + e < PW) T[r * PW + c + e] = v[e];
+      }
+    }
+  } else {
+    for (int idx = tid; idx < rows * PW; idx += 256) {
+      const int r = idx / PW, c = idx - r * PW;
+      const long long gy = gy0 + r, gx = gx0 + c;
+      float v = 0.f;
+      if (gy >= 0 && gy < h && gx >= 0 && gx < w) {
+        const size_t e = (size_t)gy * w + (size_t)gx;
+        v = bf_src<SMOOTH>(pb[e], SMOOTH ? pb2[e] : 0.f, one_minus_a, floor_m);
+      }
+      T[idx] = v;
+    }
+  }
+}
+
+// The barrier after the staging of T, the row pass and the column pass: q[o] is the blurred value of tile pixel
+// (4 (tid / 64) + o, tid % 64).  REV indexes both tap vectors in reverse (the backward step's adjoint blur).
+template <bool REV>
+__device__ __forceinline__ void bf_passes(const float* T, float* mid, const float* __restrict__ taps, int R, bool skip, int b,
+                                          float* q) {
   const int tid = threadIdx.x;
   const int rows = BF_TH + 2 * R, PW = bf_pitch(R), K = 2 * R + 1;
-  const size_t n = (size_t)h * w;
   __syncthreads();
   if (!skip) {
     // row pass: mid[r][x] = sum_j kx[2R - j] T[r][x + j], four consecutive x per lane from 16-byte pieces of the row
@@ -149,7 +151,7 @@ __device__ __forceinline__ void bf_blur_measure(const float* T, float* mid, cons
         for (int jj = 0; jj < 4; ++jj) {
           const int j = 4 * m + jj;
           if (j < K) {
-            const float k = kx[2 * R - j];
+            const float k = kx[REV ? j : 2 * R - j];
             a0 = fmaf(k, wv[jj], a0);
             a1 = fmaf(k, wv[jj + 1], a1);
             a2 = fmaf(k, wv[jj + 2], a2);
@@ -164,14 +166,14 @@ __device__ __forceinline__ void bf_blur_measure(const float* T, float* mid, cons
   __syncthreads();
   // column pass: wave s owns tile rows 4s .. 4s + 3, lanes along x
   const int tx = tid & 63, s4 = (tid >> 6) * 4;
-  float q[4] = {0.f, 0.f, 0.f, 0.f};
+  q[0] = q[1] = q[2] = q[3] = 0.f;
   if (!skip) {
     const float* ky = taps + (size_t)b * 2 * K;
     const float* mc = mid + s4 * BF_TW + tx;
     float w0 = mc[0], w1 = mc[BF_TW], w2 = mc[2 * BF_TW];
     for (int i = 0; i < K; ++i) {
       const float w3 = mc[(i + 3) * BF_TW];
-      const float k = ky[2 * R - i];
+      const float k = ky[REV ? i : 2 * R - i];
       q[0] = fmaf(k, w0, q[0]);
       q[1] = fmaf(k, w1, q[1]);
       q[2] = fmaf(k, w2, q[2]);
@@ -179,7 +181,21 @@ __device__ __forceinline__ void bf_blur_measure(const float* T, float* mid, cons
       w0 = w1; w1 = w2; w2 = w3;
     }
   }
-  // measure, write U, tile record
+}
+
+// The product, the output map(s) and the tile's record.  Forward: aux = heat, m = fma(1 - a, heat, floor), U = q m into post.
+// SMOOTH: aux = alpha, m = alpha, V = q alpha into post and q itself into bout.
+template <bool SMOOTH>
+__device__ __forceinline__ void bf_epilogue(const float* q, const float* __restrict__ aux, float one_minus_a, float floor_m,
+                                            bool skip, float* __restrict__ post, float* __restrict__ bout,
+                                            double* __restrict__ scratch, int b, int tile, int ntiles, int y0, int x0, int h,
+                                            int w) {
+  __shared__ double red[4][BF_NSUM];
+  __shared__ float rv[2][4];
+  __shared__ int ri[2][4];
+  const int tid = threadIdx.x;
+  const int tx = tid & 63, s4 = (tid >> 6) * 4;
+  const size_t n = (size_t)h * w;
   double acc[BF_NSUM];
 #pragma unroll
   for (int k = 0; k < BF_NSUM; ++k) acc[k] = 0.0;
@@ -191,9 +207,13 @@ __device__ __forceinline__ void bf_blur_measure(const float* T, float* mid, cons
       const int y = y0 + s4 + o;
       if (y < h) {
         const size_t e = (size_t)y * w + x;
-        const float mv = fmaf(one_minus_a, heat[(size_t)b * n + e], floor_m);
+        const float av = aux[(size_t)b * n + e];
+        const float mv = SMOOTH ? av : fmaf(one_minus_a, av, floor_m);
         const float uv = q[o] * mv;
-        if (!skip) post[(size_t)b * n + e] = uv;
+        if (!skip) {
+          post[(size_t)b * n + e] = uv;
+          if (SMOOTH) bout[(size_t)b * n + e] = q[o];
+        }
         acc[0] += (double)q[o];
         bf_moments(acc + 1, uv, y, x);
         bf_moments(acc + 7, mv, y, x);
@@ -232,6 +252,68 @@ __device__ __forceinline__ void bf_blur_measure(const float* T, float* mid, cons
   }
 }
 
+// Everything after the staging of T (the moved prior of the tile with its R halo), for both predict kernels: the barrier, the
+// row pass, the column pass, the measure, U and the tile's record.
+__device__ __forceinline__ void bf_blur_measure(const float* T, float* mid, const float* __restrict__ heat,
+                                                const float* __restrict__ taps, int R, float one_minus_a, float floor_m,
+                                                bool skip, float* __restrict__ post, double* __restrict__ scratch, int b,
+                                                int tile, int ntiles, int y0, int x0, int h, int w) {
+  float q[4];
+  bf_passes<false>(T, mid, taps, R, skip, b, q);
+  bf_epilogue<false>(q, heat, one_minus_a, floor_m, skip, post, nullptr, scratch, b, tile, ntiles, y0, x0, h, w);
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void belief_predict_kernel(const float* __restrict__ prior, const float* __restrict__ heat,
+                                                             const int* __restrict__ offsets, const float* __restrict__ taps,
+                                                             int R, float one_minus_a, float floor_m,
+                                                             const int* __restrict__ reset, float* __restrict__ post,
+                                                             double* __restrict__ scratch, int h, int w, int ntx, int nty) {
+  extern __shared__ cc_f32x4 bf_smem[];
+  const int ntiles = ntx * nty;
+  const int b = blockIdx.x / ntiles, tile = blockIdx.x - b * ntiles;
+  const int y0 = (tile / ntx) * BF_TH, x0 = (tile % ntx) * BF_TW;
+  const int rows = BF_TH + 2 * R, PW = bf_pitch(R);
+  float* T = reinterpret_cast<float*>(bf_smem);                  // [rows][PW]: T[r][c] = prior(y0 + r - R - oy, x0 + c - R - ox)
+  float* mid = T + rows * PW;                                    // [rows][BF_TW]: the row pass
+  const bool skip = reset != nullptr && reset[b] != 0;           // a reset track starts from the measurement: no predict
+  if (!skip) {
+    const long long oy = offsets[2 * b], ox = offsets[2 * b + 1];
+    bf_stage_shift<VEC, false>(T, prior + (size_t)b * h * w, nullptr, one_minus_a, floor_m, (long long)y0 - R - oy,
+                               (long long)x0 - R - ox, rows, PW, h, w);
+  }
+  bf_blur_measure(T, mid, heat, taps, R, one_minus_a, floor_m, skip, post, scratch, b, tile, ntiles, y0, x0, h, w);
+}
+
+// Launch one of the backward step (tracking.smooth_step_spec): the forward step's own offsets and taps, used the other way
+// round — T[r][c] = G(y0 + r - R + oy, x0 + c - R + ox) and the taps in reverse, B'[y,x] = sum_ij ky[i+R] kx[j+R]
+// G[y + oy + i, x + ox + j].  The sign lives in the 64-bit index arithmetic: no offset is negated.
+template <bool VEC>
+__global__ __launch_bounds__(256) void belief_smooth_kernel(const float* __restrict__ beta, const float* __restrict__ heat,
+                                                            const float* __restrict__ alpha, const int* __restrict__ offsets,
+                                                            const float* __restrict__ taps, int R, float one_minus_a,
+                                                            float floor_m, const int* __restrict__ cut,
+                                                            float* __restrict__ beta_out, float* __restrict__ smooth,
+                                                            double* __restrict__ scratch, int h, int w, int ntx, int nty) {
+  extern __shared__ cc_f32x4 bf_smem[];
+  const int ntiles = ntx * nty;
+  const int b = blockIdx.x / ntiles, tile = blockIdx.x - b * ntiles;
+  const int y0 = (tile / ntx) * BF_TH, x0 = (tile % ntx) * BF_TW;
+  const int rows = BF_TH + 2 * R, PW = bf_pitch(R);
+  float* T = reinterpret_cast<float*>(bf_smem);
+  float* mid = T + rows * PW;
+  const bool skip = cut != nullptr && cut[b] != 0;               // the last frame of its segment: no message to bring back
+  if (!skip) {
+    const long long oy = offsets[2 * b], ox = offsets[2 * b + 1];
+    const size_t n = (size_t)h * w;
+    bf_stage_shift<VEC, true>(T, heat + (size_t)b * n, beta + (size_t)b * n, one_minus_a, floor_m, (long long)y0 - R + oy,
+                              (long long)x0 - R + ox, rows, PW, h, w);
+  }
+  float q[4];
+  bf_passes<true>(T, mid, taps, R, skip, b, q);
+  bf_epilogue<true>(q, alpha, one_minus_a, floor_m, skip, smooth, beta_out, scratch, b, tile, ntiles, y0, x0, h, w);
+}
+
 // (a0 y + a1 x) + a2 with every product and every sum rounded on its own, as numpy evaluates the specification's expression.
 // The operators are written out under contract(off): __dmul_rn / __dadd_rn are plain inline `*` and `+` in this toolchain, and
 // the compiler fuses them into a multiply-add across the call (seen in the ISA) — the pragma only governs what it encloses.
@@ -243,73 +325,124 @@ __device__ __forceinline__ double bf_affine(double a0, double a1, double a2, dou
   return s + a2;
 }
 
-// Launch one of the rigid step (tracking.step_rigid_spec): T holds W, the bilinear sample of the prior through the track's
-// inverse map, on the (16 + 2R) x (64 + 2R) pixels the tile's blur reads — the halo is warped too, the blur runs over W.  The
+// tracking.invert_motion on the device, operation for operation: the general 2 x 2 inverse in double with every product, sum
+// and quotient rounded on its own; NaN rows (which sample nothing) for a singular or non-finite row.
+__device__ __forceinline__ void bf_invert_motion(const double* __restrict__ m, double* o) {
+#pragma clang fp contract(off)
+  const double a00 = m[0], a01 = m[1], a02 = m[2], a10 = m[3], a11 = m[4], a12 = m[5];
+  const double p = a00 * a11;
+  const double r = a01 * a10;
+  const double det = p - r;
+  bool ok = fabs(det) < (double)INFINITY && det != 0.0;
+#pragma unroll
+  for (int k = 0; k < 6; ++k) ok = ok && fabs(m[k]) < (double)INFINITY;
+  const double b00 = a11 / det, b01 = -a01 / det, b10 = -a10 / det, b11 = a00 / det;
+  const double t0 = b00 * a02, t1 = b01 * a12, t2 = b10 * a02, t3 = b11 * a12;
+  const double s0 = t0 + t1, s1 = t2 + t3;
+  o[0] = ok ? b00 : NAN; o[1] = ok ? b01 : NAN; o[2] = ok ? -s0 : NAN;
+  o[3] = ok ? b10 : NAN; o[4] = ok ? b11 : NAN; o[5] = ok ? -s1 : NAN;
+}
+
+// Stage W, the bilinear sample of a map through an inverse map, on the (16 + 2R) x (64 + 2R) pixels the tile's blur reads — the
+// halo is warped too, the blur runs over W.  The
 // source coordinates are computed per sample in double from the integer pixel with separately rounded products and sums in the
 // order of the specification (no contraction, no stepping), so floor() and the fp32 weights are the specification's; the range
 // test is done on the doubles (any motion row, NaN and inf included, reads nothing outside the prior).  The four taps are
 // gathered from global memory (1 MB per track at 512 x 512: L2-resident, 2-D local); columns of T beyond 64 + 2R are loaded by
-// the row pass but enter no sum.
+// the row pass but enter no sum.  SMOOTH gathers the four taps of both maps (heat, beta) and samples G = M beta.
+template <bool SMOOTH>
+__device__ __forceinline__ void bf_stage_warp(float* T, const float* __restrict__ pb, const float* __restrict__ pb2,
+                                              const double* m, float one_minus_a, float floor_m, int R, int y0, int x0, int h,
+                                              int w) {
+  const int tid = threadIdx.x;
+  const int rows = BF_TH + 2 * R, cols = BF_TW + 2 * R, PW = bf_pitch(R);
+  const double a00 = m[0], a01 = m[1], a02 = m[2], a10 = m[3], a11 = m[4], a12 = m[5];
+  const double hd = (double)h, wd = (double)w;
+  for (int idx = tid; idx < rows * cols; idx += 256) {
+    const int r = idx / cols, c = idx - r * cols;
+    const double y = (double)(y0 + r - R), x = (double)(x0 + c - R);
+    const double sy = bf_affine(a00, a01, a02, y, x), sx = bf_affine(a10, a11, a12, y, x);
+    float v = 0.f;
+    if (sy > -1.0 && sy < hd && sx > -1.0 && sx < wd) {        // false for NaN and inf; only then to int
+      const double fy0 = floor(sy), fx0 = floor(sx);
+      const double fy = sy - fy0, fx = sx - fx0;
+      const int iy = (int)fy0, ix = (int)fx0;                  // -1 .. h - 1, -1 .. w - 1
+      const float wy1 = (float)fy, wy0 = (float)(1.0 - fy);
+      const float wx1 = (float)fx, wx0 = (float)(1.0 - fx);
+      const bool ya = iy >= 0, yb = iy + 1 < h, xa = ix >= 0, xb = ix + 1 < w;
+      const long long e = (long long)iy * w + ix;              // dereferenced only under the guards
+      float v00 = 0.f, v01 = 0.f, v10 = 0.f, v11 = 0.f;
+      if (ya && xa) v00 = bf_src<SMOOTH>(pb[e], SMOOTH ? pb2[e] : 0.f, one_minus_a, floor_m);
+      if (ya && xb) v01 = bf_src<SMOOTH>(pb[e + 1], SMOOTH ? pb2[e + 1] : 0.f, one_minus_a, floor_m);
+      if (yb && xa) v10 = bf_src<SMOOTH>(pb[e + w], SMOOTH ? pb2[e + w] : 0.f, one_minus_a, floor_m);
+      if (yb && xb) v11 = bf_src<SMOOTH>(pb[e + w + 1], SMOOTH ? pb2[e + w + 1] : 0.f, one_minus_a, floor_m);
+      const float top = fmaf(wx1, v01, __fmul_rn(wx0, v00));
+      const float bot = fmaf(wx1, v11, __fmul_rn(wx0, v10));
+      v = fmaf(wy1, bot, __fmul_rn(wy0, top));
+    }
+    T[r * PW + c] = v;
+  }
+}
+
+// Launch one of the rigid step (tracking.step_rigid_spec): T holds W, the prior resampled through the track's inverse map.
 __global__ __launch_bounds__(256) void belief_predict_rigid_kernel(const float* __restrict__ prior, const float* __restrict__ heat,
                                                                    const double* __restrict__ motion, const float* __restrict__ taps,
                                                                    int R, float one_minus_a, float floor_m,
                                                                    const int* __restrict__ reset, float* __restrict__ post,
                                                                    double* __restrict__ scratch, int h, int w, int ntx, int nty) {
   extern __shared__ cc_f32x4 bf_smem[];
-  const int tid = threadIdx.x;
   const int ntiles = ntx * nty;
   const int b = blockIdx.x / ntiles, tile = blockIdx.x - b * ntiles;
   const int y0 = (tile / ntx) * BF_TH, x0 = (tile % ntx) * BF_TW;
-  const int rows = BF_TH + 2 * R, cols = BF_TW + 2 * R, PW = bf_pitch(R);
+  const int rows = BF_TH + 2 * R, PW = bf_pitch(R);
   float* T = reinterpret_cast<float*>(bf_smem);                  // [rows][PW]: T[r][c] = W(y0 + r - R, x0 + c - R), c < cols
   float* mid = T + rows * PW;
   const bool skip = reset != nullptr && reset[b] != 0;
   if (!skip) {
     const double* m = motion + (size_t)b * 6;
-    const double a00 = m[0], a01 = m[1], a02 = m[2], a10 = m[3], a11 = m[4], a12 = m[5];
-    const double hd = (double)h, wd = (double)w;
-    const float* pb = prior + (size_t)b * h * w;
-    for (int idx = tid; idx < rows * cols; idx += 256) {
-      const int r = idx / cols, c = idx - r * cols;
-      const double y = (double)(y0 + r - R), x = (double)(x0 + c - R);
-      const double sy = bf_affine(a00, a01, a02, y, x), sx = bf_affine(a10, a11, a12, y, x);
-      float v = 0.f;
-      if (sy > -1.0 && sy < hd && sx > -1.0 && sx < wd) {        // false for NaN and inf; only then to int
-        const double fy0 = floor(sy), fx0 = floor(sx);
-        const double fy = sy - fy0, fx = sx - fx0;
-        const int iy = (int)fy0, ix = (int)fx0;                  // -1 .. h - 1, -1 .. w - 1
-        const float wy1 = (float)fy, wy0 = (float)(1.0 - fy);
-        const float wx1 = (float)fx, wx0 = (float)(1.0 - fx);
-        const bool ya = iy >= 0, yb = iy + 1 < h, xa = ix >= 0, xb = ix + 1 < w;
-        const long long e = (long long)iy * w + ix;              // dereferenced only under the guards
-        const float v00 = (ya && xa) ? pb[e] : 0.f, v01 = (ya && xb) ? pb[e + 1] : 0.f;
-        const float v10 = (yb && xa) ? pb[e + w] : 0.f, v11 = (yb && xb) ? pb[e + w + 1] : 0.f;
-        const float top = fmaf(wx1, v01, __fmul_rn(wx0, v00));
-        const float bot = fmaf(wx1, v11, __fmul_rn(wx0, v10));
-        v = fmaf(wy1, bot, __fmul_rn(wy0, top));
-      }
-      T[r * PW + c] = v;
-    }
+    const double mm[6] = {m[0], m[1], m[2], m[3], m[4], m[5]};
+    bf_stage_warp<false>(T, prior + (size_t)b * h * w, nullptr, mm, one_minus_a, floor_m, R, y0, x0, h, w);
   }
   bf_blur_measure(T, mid, heat, taps, R, one_minus_a, floor_m, skip, post, scratch, b, tile, ntiles, y0, x0, h, w);
 }
 
-template <bool VEC>
-__global__ __launch_bounds__(256) void belief_finish_kernel(const float* __restrict__ heat, const float* __restrict__ ori,
-                                                            float one_minus_a, float floor_m, const int* __restrict__ reset,
-                                                            float* __restrict__ post, const double* __restrict__ scratch,
-                                                            double* __restrict__ rows, int h, int w, int ntiles, int slices,
-                                                            int slice_len) {
+// Launch one of the rigid backward step (tracking.smooth_step_rigid_spec): T holds G = M beta of frame t resampled along the
+// REVERSE motion — the forward step's motion row, inverted here — then the reversed-tap blur and the shared epilogue.  A
+// bilinear gather's adjoint would be a scatter: this is the same continuous model discretised the other way, not the exact
+// adjoint of the rigid predict (for whole-pixel shifts and quarter turns the two coincide).
+__global__ __launch_bounds__(256) void belief_smooth_rigid_kernel(const float* __restrict__ beta, const float* __restrict__ heat,
+                                                                  const float* __restrict__ alpha,
+                                                                  const double* __restrict__ motion,
+                                                                  const float* __restrict__ taps, int R, float one_minus_a,
+                                                                  float floor_m, const int* __restrict__ cut,
+                                                                  float* __restrict__ beta_out, float* __restrict__ smooth,
+                                                                  double* __restrict__ scratch, int h, int w, int ntx, int nty) {
+  extern __shared__ cc_f32x4 bf_smem[];
+  const int ntiles = ntx * nty;
+  const int b = blockIdx.x / ntiles, tile = blockIdx.x - b * ntiles;
+  const int y0 = (tile / ntx) * BF_TH, x0 = (tile % ntx) * BF_TW;
+  const int rows = BF_TH + 2 * R, PW = bf_pitch(R);
+  float* T = reinterpret_cast<float*>(bf_smem);
+  float* mid = T + rows * PW;
+  const bool skip = cut != nullptr && cut[b] != 0;
+  if (!skip) {
+    double back[6];
+    bf_invert_motion(motion + (size_t)b * 6, back);
+    const size_t n = (size_t)h * w;
+    bf_stage_warp<true>(T, heat + (size_t)b * n, beta + (size_t)b * n, back, one_minus_a, floor_m, R, y0, x0, h, w);
+  }
+  float q[4];
+  bf_passes<true>(T, mid, taps, R, skip, b, q);
+  bf_epilogue<true>(q, alpha, one_minus_a, floor_m, skip, smooth, beta_out, scratch, b, tile, ntiles, y0, x0, h, w);
+}
+
+// The track's records, merged in a fixed order by every workgroup of launch two: lane-strided, butterfly, waves 0..3.  fin
+// [BF_NSUM], fv [2], fi [2] are the caller's shared arrays; ends with a barrier.
+__device__ __forceinline__ void bf_merge_records(const double* __restrict__ rec, int ntiles, double* fin, float* fv, int* fi) {
   __shared__ double red[4][BF_NSUM];
   __shared__ float rv[2][4];
   __shared__ int ri[2][4];
-  __shared__ double fin[BF_NSUM];
-  __shared__ float fv[2];
-  __shared__ int fi[2];
   const int tid = threadIdx.x;
-  const int b = blockIdx.x / slices, sl = blockIdx.x - b * slices;
-  const double* rec = scratch + (size_t)b * ntiles * BF_REC;
-  // the track's records, merged in a fixed order: lane-strided, butterfly, waves 0..3
   double acc[BF_NSUM];
 #pragma unroll
   for (int k = 0; k < BF_NSUM; ++k) acc[k] = 0.0;
@@ -347,6 +480,39 @@ __global__ __launch_bounds__(256) void belief_finish_kernel(const float* __restr
     fv[1] = am.v; fi[1] = am.i == BF_NONE ? 0 : am.i;
   }
   __syncthreads();
+}
+
+// The 14 columns of a track's row from the merged record: bi the arg-max index, best the unscaled value there, mom the six
+// moment sums of the map the state selected, Z = mom[0], S the record's first sum.
+__device__ __forceinline__ void bf_write_row(double* __restrict__ r, const float* __restrict__ ori, int b, size_t n, int w,
+                                             int bi, float best, float inv, const double* mom, double Z, int state, double S) {
+  const float c = ori[((size_t)b * 2 + 0) * n + bi], s = ori[((size_t)b * 2 + 1) * n + bi];
+  double ang = NAN;
+  if (fabsf(c) <= 1.0f && fabsf(s) <= 1.0f) ang = angle_deg_f64((double)c, s < 0.0f);
+  const double my = mom[1] / Z, mx = mom[2] / Z;
+  r[0] = (double)(bi / w); r[1] = (double)(bi % w);
+  r[2] = (double)(best * inv);
+  r[3] = (double)c; r[4] = (double)s; r[5] = ang;
+  r[6] = Z; r[7] = (double)state;
+  r[8] = my; r[9] = mx;
+  r[10] = mom[3] / Z - my * my;
+  r[11] = mom[4] / Z - mx * mx;
+  r[12] = mom[5] / Z - my * mx;
+  r[13] = S;
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void belief_finish_kernel(const float* __restrict__ heat, const float* __restrict__ ori,
+                                                            float one_minus_a, float floor_m, const int* __restrict__ reset,
+                                                            float* __restrict__ post, const double* __restrict__ scratch,
+                                                            double* __restrict__ rows, int h, int w, int ntiles, int slices,
+                                                            int slice_len) {
+  __shared__ double fin[BF_NSUM];
+  __shared__ float fv[2];
+  __shared__ int fi[2];
+  const int tid = threadIdx.x;
+  const int b = blockIdx.x / slices, sl = blockIdx.x - b * slices;
+  bf_merge_records(scratch + (size_t)b * ntiles * BF_REC, ntiles, fin, fv, fi);
   int rst = (reset != nullptr && reset[b] != 0) ? 1 : 0;
   double Z = fin[1];
   if (!rst && !(Z > 0.0 && Z < (double)INFINITY)) rst = 2;
@@ -376,21 +542,63 @@ __global__ __launch_bounds__(256) void belief_finish_kernel(const float* __restr
     for (size_t i = e0 + tid; i < e1; i += 256) pb[i] = (rst ? fmaf(one_minus_a, hb[i], floor_m) : pb[i]) * inv;
   }
   if (sl != 0 || tid != 0) return;
-  const int bi = fi[sel];
-  const float c = ori[((size_t)b * 2 + 0) * n + bi], s = ori[((size_t)b * 2 + 1) * n + bi];
-  double ang = NAN;
-  if (fabsf(c) <= 1.0f && fabsf(s) <= 1.0f) ang = angle_deg_f64((double)c, s < 0.0f);
-  const double my = mom[1] / Z, mx = mom[2] / Z;
-  double* r = rows + (size_t)b * 14;
-  r[0] = (double)(bi / w); r[1] = (double)(bi % w);
-  r[2] = (double)(fv[sel] * inv);
-  r[3] = (double)c; r[4] = (double)s; r[5] = ang;
-  r[6] = Z; r[7] = (double)rst;
-  r[8] = my; r[9] = mx;
-  r[10] = mom[3] / Z - my * my;
-  r[11] = mom[4] / Z - mx * mx;
-  r[12] = mom[5] / Z - my * mx;
-  r[13] = fin[0];
+  bf_write_row(rows + (size_t)b * 14, ori, b, n, w, fi[sel], fv[sel], inv, mom, Z, rst, fin[0]);
+}
+
+// Launch two of the backward step: state 1 for a cut track, 2 when not (Z > 0 and finite and S > 0 and finite); state 0 scales
+// V by (float)(1 / Z) and B' by (float)(1 / S); otherwise smooth = alpha (float)(1 / sum alpha) and the message is uniform.
+template <bool VEC>
+__global__ __launch_bounds__(256) void belief_smooth_finish_kernel(const float* __restrict__ alpha, const float* __restrict__ ori,
+                                                                   const int* __restrict__ cut, float* __restrict__ beta_out,
+                                                                   float* __restrict__ smooth,
+                                                                   const double* __restrict__ scratch,
+                                                                   double* __restrict__ rows, int h, int w, int ntiles,
+                                                                   int slices, int slice_len) {
+  __shared__ double fin[BF_NSUM];
+  __shared__ float fv[2];
+  __shared__ int fi[2];
+  const int tid = threadIdx.x;
+  const int b = blockIdx.x / slices, sl = blockIdx.x - b * slices;
+  bf_merge_records(scratch + (size_t)b * ntiles * BF_REC, ntiles, fin, fv, fi);
+  int state = (cut != nullptr && cut[b] != 0) ? 1 : 0;
+  const double S = fin[0];
+  double Z = fin[1];
+  if (!state && !(Z > 0.0 && Z < (double)INFINITY && S > 0.0 && S < (double)INFINITY)) state = 2;
+  const int sel = state ? 1 : 0;                                 // the alpha record serves the fallback
+  const double* mom = fin + 1 + 6 * sel;
+  Z = mom[0];
+  const size_t n = (size_t)h * w;
+  const float inv = (float)(1.0 / Z);
+  const float invs = state ? (float)(1.0 / (double)n) : (float)(1.0 / S);
+  const float* ab = alpha + (size_t)b * n;
+  float* sb = smooth + (size_t)b * n;
+  float* bb = beta_out + (size_t)b * n;
+  const size_t e0 = (size_t)sl * slice_len, e1 = e0 + slice_len < n ? e0 + slice_len : n;
+  if (VEC) {                                                     // n % 4 == 0, slice_len % 4 == 0, 16-byte aligned maps
+    for (size_t i = e0 + 4 * (size_t)tid; i < e1; i += 1024) {
+      cc_f32x4 v, m;
+      if (state) {
+        v = *reinterpret_cast<const cc_f32x4*>(ab + i);
+        m = (cc_f32x4){invs, invs, invs, invs};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] *= inv;
+      } else {
+        v = *reinterpret_cast<const cc_f32x4*>(sb + i);
+        m = *reinterpret_cast<const cc_f32x4*>(bb + i);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { v[k] *= inv; m[k] *= invs; }
+      }
+      *reinterpret_cast<cc_f32x4*>(sb + i) = v;
+      *reinterpret_cast<cc_f32x4*>(bb + i) = m;
+    }
+  } else {
+    for (size_t i = e0 + tid; i < e1; i += 256) {
+      sb[i] = (state ? ab[i] : sb[i]) * inv;
+      bb[i] = state ? invs : bb[i] * invs;
+    }
+  }
+  if (sl != 0 || tid != 0) return;
+  bf_write_row(rows + (size_t)b * 14, ori, b, n, w, fi[sel], fv[sel], inv, mom, Z, state, S);
 }
 
 static bool bf_tiles(int h, int w, int* ntx, int* nty) {
@@ -413,43 +621,70 @@ extern "C" int ccvpe_belief_partials(int h, int w) {
 
 namespace ccvpe {
 
-// The argument checks the two step entry points share; `move` is the step's own motion input (offsets / motion).
-static int bf_check(const float* prior, const float* heat, const float* ori, const void* move, const float* taps, int radius,
-                    float outlier, const int* reset, float* post, double* scratch, double* rows, int batch, int h, int w,
-                    int* ntx, int* nty) {
-  if (batch <= 0 || !bf_tiles(h, w, ntx, nty)) return fail(CCVPE_EINVAL, "belief_step: bad shape");
+static bool bf_overlap(const void* a, size_t abytes, const void* b, size_t bbytes) {
+  const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+  return a0 < b0 + bbytes && b0 < a0 + abytes;
+}
+
+// The argument checks the step entry points share; `move` is the step's own motion input (offsets / motion), `who` the entry's
+// name in the message.  The backward step passes beta as prior, cut as reset and smooth as post.
+static int bf_check(const char* who, const float* prior, const float* heat, const float* ori, const void* move, const float* taps,
+                    int radius, float outlier, const int* reset, float* post, double* scratch, double* rows, int batch, int h,
+                    int w, int* ntx, int* nty) {
+  if (batch <= 0 || !bf_tiles(h, w, ntx, nty)) return fail(CCVPE_EINVAL, "%s: bad shape", who);
   const long long ntiles = (long long)*ntx * *nty;
-  if (ntiles * batch > 0x7fffffffLL) return fail(CCVPE_EINVAL, "belief_step: batch x tiles > 2^31");
-  if (radius < 0 || radius > 32) return fail(CCVPE_EINVAL, "belief_step: radius %d outside [0, 32]", radius);
-  if (!(outlier >= 0.f && outlier <= 1.f)) return fail(CCVPE_EINVAL, "belief_step: outlier outside [0, 1]");
+  if (ntiles * batch > 0x7fffffffLL) return fail(CCVPE_EINVAL, "%s: batch x tiles > 2^31", who);
+  if (radius < 0 || radius > 32) return fail(CCVPE_EINVAL, "%s: radius %d outside [0, 32]", who, radius);
+  if (!(outlier >= 0.f && outlier <= 1.f)) return fail(CCVPE_EINVAL, "%s: outlier outside [0, 1]", who);
   if (!prior || !heat || !ori || !move || !taps || !post || !scratch || !rows)
-    return fail(CCVPE_EINVAL, "belief_step: null pointer");
+    return fail(CCVPE_EINVAL, "%s: null pointer", who);
   if ((reinterpret_cast<uintptr_t>(rows) | reinterpret_cast<uintptr_t>(scratch)) & 7)
-    return fail(CCVPE_EINVAL, "belief_step: rows and scratch must be 8-byte aligned");
+    return fail(CCVPE_EINVAL, "%s: rows and scratch must be 8-byte aligned", who);
   if ((reinterpret_cast<uintptr_t>(prior) | reinterpret_cast<uintptr_t>(heat) | reinterpret_cast<uintptr_t>(ori) |
        reinterpret_cast<uintptr_t>(post) | reinterpret_cast<uintptr_t>(move) | reinterpret_cast<uintptr_t>(taps) |
        reinterpret_cast<uintptr_t>(reset)) & 3)
-    return fail(CCVPE_EINVAL, "belief_step: float and int arrays must be 4-byte aligned");
+    return fail(CCVPE_EINVAL, "%s: float and int arrays must be 4-byte aligned", who);
   const size_t n = (size_t)h * w, bytes = (size_t)batch * n * sizeof(float);
-  const uintptr_t p0 = reinterpret_cast<uintptr_t>(prior), q0 = reinterpret_cast<uintptr_t>(post);
-  if (p0 < q0 + bytes && q0 < p0 + bytes) return fail(CCVPE_EINVAL, "belief_step: prior and post overlap");
+  if (bf_overlap(prior, bytes, post, bytes)) return fail(CCVPE_EINVAL, "%s: prior and post overlap", who);
   // launch one writes U into post and launch two reads heat (a reset recomputes M from it) and ori (the row) afterwards
-  const uintptr_t h0 = reinterpret_cast<uintptr_t>(heat), o0 = reinterpret_cast<uintptr_t>(ori);
-  if (h0 < q0 + bytes && q0 < h0 + bytes) return fail(CCVPE_EINVAL, "belief_step: heat and post overlap");
-  if (o0 < q0 + bytes && q0 < o0 + 2 * bytes) return fail(CCVPE_EINVAL, "belief_step: ori and post overlap");
+  if (bf_overlap(heat, bytes, post, bytes)) return fail(CCVPE_EINVAL, "%s: heat and post overlap", who);
+  if (bf_overlap(ori, 2 * bytes, post, bytes)) return fail(CCVPE_EINVAL, "%s: ori and post overlap", who);
   return CCVPE_OK;
 }
 
-// Launch two: ~1024 workgroups scale the maps; each merges the track's records first
+// What the backward step checks beyond bf_check: alpha and beta_out, and that neither output shares memory with the other or
+// with any input map — launch two reads alpha, heat's neighbours in launch one's halo and ori after launch one has written.
+static int bf_check_smooth(const char* who, const float* beta, const float* heat, const float* alpha, const float* ori,
+                           float* beta_out, float* smooth, int batch, int h, int w) {
+  if (!alpha || !beta_out) return fail(CCVPE_EINVAL, "%s: null pointer", who);
+  if ((reinterpret_cast<uintptr_t>(alpha) | reinterpret_cast<uintptr_t>(beta_out)) & 3)
+    return fail(CCVPE_EINVAL, "%s: float and int arrays must be 4-byte aligned", who);
+  const size_t bytes = (size_t)batch * h * w * sizeof(float);
+  if (bf_overlap(alpha, bytes, smooth, bytes)) return fail(CCVPE_EINVAL, "%s: alpha and smooth overlap", who);
+  if (bf_overlap(smooth, bytes, beta_out, bytes)) return fail(CCVPE_EINVAL, "%s: smooth and beta_out overlap", who);
+  if (bf_overlap(beta, bytes, beta_out, bytes)) return fail(CCVPE_EINVAL, "%s: beta and beta_out overlap", who);
+  if (bf_overlap(heat, bytes, beta_out, bytes)) return fail(CCVPE_EINVAL, "%s: heat and beta_out overlap", who);
+  if (bf_overlap(alpha, bytes, beta_out, bytes)) return fail(CCVPE_EINVAL, "%s: alpha and beta_out overlap", who);
+  if (bf_overlap(ori, 2 * bytes, beta_out, bytes)) return fail(CCVPE_EINVAL, "%s: ori and beta_out overlap", who);
+  return CCVPE_OK;
+}
+
+// The slices of launch two: ~1024 workgroups scale the maps; each merges the track's records first
+static int bf_slices(const char* who, int batch, size_t n, int* slices, int* slice_len) {
+  int s = (1024 + batch - 1) / batch;
+  s = s < 1 ? 1 : (s > 64 ? 64 : s);
+  const size_t per = (n + s - 1) / s;
+  *slice_len = (int)((per + 3) & ~(size_t)3);
+  *slices = (int)((n + *slice_len - 1) / *slice_len);
+  if ((long long)*slices * batch > 0x7fffffffLL) return fail(CCVPE_EINVAL, "%s: batch x slices > 2^31", who);
+  return CCVPE_OK;
+}
+
 static int bf_finish(const float* heat, const float* ori, float one_minus_a, float floor_m, const int* reset, float* post,
                      double* scratch, double* rows, int batch, int h, int w, long long ntiles, hipStream_t st) {
   const size_t n = (size_t)h * w;
-  int slices = (1024 + batch - 1) / batch;
-  slices = slices < 1 ? 1 : (slices > 64 ? 64 : slices);
-  const size_t per = (n + slices - 1) / slices;
-  const int slice_len = (int)((per + 3) & ~(size_t)3);
-  slices = (int)((n + slice_len - 1) / slice_len);
-  if ((long long)slices * batch > 0x7fffffffLL) return fail(CCVPE_EINVAL, "belief_step: batch x slices > 2^31");
+  int slices, slice_len;
+  if (int rc = bf_slices("belief_step", batch, n, &slices, &slice_len)) return rc;
   const bool vec2 = (n % 4) == 0 && aligned16(heat) && aligned16(post);
   const dim3 grid2((unsigned)(slices * batch));
   if (vec2)
@@ -461,13 +696,30 @@ static int bf_finish(const float* heat, const float* ori, float one_minus_a, flo
   return check_launch("belief_finish_kernel");
 }
 
+static int bf_smooth_finish(const float* alpha, const float* ori, const int* cut, float* beta_out, float* smooth, double* scratch,
+                            double* rows, int batch, int h, int w, long long ntiles, hipStream_t st) {
+  const size_t n = (size_t)h * w;
+  int slices, slice_len;
+  if (int rc = bf_slices("belief_smooth_step", batch, n, &slices, &slice_len)) return rc;
+  const bool vec2 = (n % 4) == 0 && aligned16(alpha) && aligned16(smooth) && aligned16(beta_out);
+  const dim3 grid2((unsigned)(slices * batch));
+  if (vec2)
+    hipLaunchKernelGGL(belief_smooth_finish_kernel<true>, grid2, dim3(256), 0, st, alpha, ori, cut, beta_out, smooth, scratch, rows,
+                       h, w, (int)ntiles, slices, slice_len);
+  else
+    hipLaunchKernelGGL(belief_smooth_finish_kernel<false>, grid2, dim3(256), 0, st, alpha, ori, cut, beta_out, smooth, scratch, rows,
+                       h, w, (int)ntiles, slices, slice_len);
+  return check_launch("belief_smooth_finish_kernel");
+}
+
 }  // namespace ccvpe
 
 extern "C" int ccvpe_belief_step_f32(const float* prior, const float* heat, const float* ori, const int* offsets,
                                      const float* taps, int radius, float outlier, const int* reset, float* post,
                                      double* scratch, double* rows, int batch, int h, int w, void* stream) {
   int ntx, nty;
-  if (int rc = bf_check(prior, heat, ori, offsets, taps, radius, outlier, reset, post, scratch, rows, batch, h, w, &ntx, &nty))
+  if (int rc = bf_check("belief_step", prior, heat, ori, offsets, taps, radius, outlier, reset, post, scratch, rows, batch, h, w,
+                        &ntx, &nty))
     return rc;
   const long long ntiles = (long long)ntx * nty;
   const size_t n = (size_t)h * w;
@@ -497,7 +749,8 @@ extern "C" int ccvpe_belief_step_rigid_f32(const float* prior, const float* heat
                                            const float* taps, int radius, float outlier, const int* reset, float* post,
                                            double* scratch, double* rows, int batch, int h, int w, void* stream) {
   int ntx, nty;
-  if (int rc = bf_check(prior, heat, ori, motion, taps, radius, outlier, reset, post, scratch, rows, batch, h, w, &ntx, &nty))
+  if (int rc = bf_check("belief_step", prior, heat, ori, motion, taps, radius, outlier, reset, post, scratch, rows, batch, h, w,
+                        &ntx, &nty))
     return rc;
   if (reinterpret_cast<uintptr_t>(motion) & 7) return fail(CCVPE_EINVAL, "belief_step_rigid: motion must be 8-byte aligned");
   const long long ntiles = (long long)ntx * nty;
@@ -511,4 +764,60 @@ extern "C" int ccvpe_belief_step_rigid_f32(const float* prior, const float* heat
                      floor_m, reset, post, scratch, h, w, ntx, nty);
   if (int rc = check_launch("belief_predict_rigid_kernel")) return rc;
   return bf_finish(heat, ori, one_minus_a, floor_m, reset, post, scratch, rows, batch, h, w, ntiles, st);
+}
+
+extern "C" int ccvpe_belief_smooth_step_f32(const float* beta, const float* heat, const float* alpha, const float* ori,
+                                            const int* offsets, const float* taps, int radius, float outlier, const int* cut,
+                                            float* beta_out, float* smooth, double* scratch, double* rows, int batch, int h,
+                                            int w, void* stream) {
+  const char* who = "belief_smooth_step";
+  int ntx, nty;
+  if (int rc = bf_check(who, beta, heat, ori, offsets, taps, radius, outlier, cut, smooth, scratch, rows, batch, h, w, &ntx, &nty))
+    return rc;
+  if (int rc = bf_check_smooth(who, beta, heat, alpha, ori, beta_out, smooth, batch, h, w)) return rc;
+  const long long ntiles = (long long)ntx * nty;
+  const size_t n = (size_t)h * w;
+  hipStream_t st = (hipStream_t)stream;
+  const float one_minus_a = 1.0f - outlier, floor_m = outlier / (float)n;
+  const int smem = (int)sizeof(float) * (BF_TH + 2 * radius) * (bf_pitch(radius) + BF_TW);
+  const bool vec1 = (w % 4) == 0 && aligned16(heat) && aligned16(beta);
+  const dim3 grid1((unsigned)(ntiles * batch));
+  if (vec1) {
+    auto kern = belief_smooth_kernel<true>;
+    static DevCache lds_set;
+    if (int rc = ensure_dyn_lds(lds_set, kern, smem, who)) return rc;
+    hipLaunchKernelGGL(kern, grid1, dim3(256), smem, st, beta, heat, alpha, offsets, taps, radius, one_minus_a, floor_m, cut,
+                       beta_out, smooth, scratch, h, w, ntx, nty);
+  } else {
+    auto kern = belief_smooth_kernel<false>;
+    static DevCache lds_set;
+    if (int rc = ensure_dyn_lds(lds_set, kern, smem, who)) return rc;
+    hipLaunchKernelGGL(kern, grid1, dim3(256), smem, st, beta, heat, alpha, offsets, taps, radius, one_minus_a, floor_m, cut,
+                       beta_out, smooth, scratch, h, w, ntx, nty);
+  }
+  if (int rc = check_launch("belief_smooth_kernel")) return rc;
+  return bf_smooth_finish(alpha, ori, cut, beta_out, smooth, scratch, rows, batch, h, w, ntiles, st);
+}
+
+extern "C" int ccvpe_belief_smooth_step_rigid_f32(const float* beta, const float* heat, const float* alpha, const float* ori,
+                                                  const double* motion, const float* taps, int radius, float outlier,
+                                                  const int* cut, float* beta_out, float* smooth, double* scratch, double* rows,
+                                                  int batch, int h, int w, void* stream) {
+  const char* who = "belief_smooth_step_rigid";
+  int ntx, nty;
+  if (int rc = bf_check(who, beta, heat, ori, motion, taps, radius, outlier, cut, smooth, scratch, rows, batch, h, w, &ntx, &nty))
+    return rc;
+  if (int rc = bf_check_smooth(who, beta, heat, alpha, ori, beta_out, smooth, batch, h, w)) return rc;
+  if (reinterpret_cast<uintptr_t>(motion) & 7) return fail(CCVPE_EINVAL, "%s: motion must be 8-byte aligned", who);
+  const long long ntiles = (long long)ntx * nty;
+  hipStream_t st = (hipStream_t)stream;
+  const float one_minus_a = 1.0f - outlier, floor_m = outlier / (float)((size_t)h * w);
+  const int smem = (int)sizeof(float) * (BF_TH + 2 * radius) * (bf_pitch(radius) + BF_TW);
+  auto kern = belief_smooth_rigid_kernel;
+  static DevCache lds_set;
+  if (int rc = ensure_dyn_lds(lds_set, kern, smem, who)) return rc;
+  hipLaunchKernelGGL(kern, dim3((unsigned)(ntiles * batch)), dim3(256), smem, st, beta, heat, alpha, motion, taps, radius,
+                     one_minus_a, floor_m, cut, beta_out, smooth, scratch, h, w, ntx, nty);
+  if (int rc = check_launch("belief_smooth_rigid_kernel")) return rc;
+  return bf_smooth_finish(alpha, ori, cut, beta_out, smooth, scratch, rows, batch, h, w, ntiles, st);
 }

@@ -314,7 +314,7 @@ def evaluate_batches(forward_fn, batches, metres_per_pixel=None, sets=None):
     return res
 
 
-def evaluate_sequence(forward_fn, batches, filt, shift_px, starts, metres_per_pixel=None, sets=None, motion=None):
+def evaluate_sequence(forward_fn, batches, filt, shift_px, starts, metres_per_pixel=None, sets=None, motion=None, smooth=False):
     """The reference's test protocol along a drive, for the raw heat-maps AND for the belief of a histogram filter
     (ccvpe_amd.tracking.HistogramFilter with one track).  `batches`: a DeviceBatches in drive order — unshuffled, one rank,
     targets=True (ValueError otherwise); shift_px [n,2] and starts [n] per sample of `batches.indices`, e.g. from
@@ -324,7 +324,15 @@ def evaluate_sequence(forward_fn, batches, filt, shift_px, starts, metres_per_pi
     the raw maps; then per frame one `filt.step` (reset first where starts says so) and one ccvpe_eval_metrics_f32 launch on the
     belief, all into device tables; ONE read-back after the loop.
     Returns {"raw": summarise(...), "filtered": summarise(...), "tracks": [n,14] (tracking.PRED_Y ... SURVIVED),
-    "raw_rows": [n,12], "filtered_rows": [n,12], "indices": [n]}."""
+    "raw_rows": [n,12], "filtered_rows": [n,12], "indices": [n]}.
+
+    smooth=True adds the forward-backward smoothed estimate (tracking.SequenceSmoother with the filter's settings: the belief
+    of every frame given the WHOLE drive).  The loop then also keeps, per frame and on the device, the heat-map, ori (2 maps),
+    the ground-truth map, gt_ori (2 maps) and the filter's posterior, plus metres per pixel and the heading: 7 fp32 maps, 7 MB
+    per frame at 512 x 512, and the smoothed beliefs (1 MB per frame) during the backward pass.  After the loop: the backward
+    pass (two launches per frame) and one ccvpe_eval_metrics_f32 launch per smoothed belief; still ONE read-back.  The result
+    gains "smoothed": summarise(...), "smoothed_rows": [n,12] and "smoothed_tracks": [n,14] (RESET holds the backward state).
+    With smooth=False the returned dict and the launches are exactly those described above."""
     from . import ops
     if not batches.targets:
         raise ValueError("evaluate_sequence needs DeviceBatches(..., targets=True): the ground truth comes from the batch")
@@ -359,6 +367,8 @@ def evaluate_sequence(forward_fn, batches, filt, shift_px, starts, metres_per_pi
     if not isinstance(mpp, dict):
         mpp_const = torch.full((max(1, batches.batch_size),), float(mpp), device=dev, dtype=torch.float64)
     k = 0
+    kept = None                                                                 # smooth: [n, ...] copies of heat, ori, gt, gt_ori, heading, m
+    posts = torch.empty((n, 1) + tuple(filt.hw), device=dev, dtype=torch.float32) if smooth else None
     for batch in batches:
         b = len(batch.indices)
         with torch.no_grad():
@@ -367,6 +377,12 @@ def evaluate_sequence(forward_fn, batches, filt, shift_px, starts, metres_per_pi
              else mpp_const[:b])
         heat, ori = out[1], out[2]
         ops.eval_metrics(heat, ori, batch.gt, batch.gt_ori, batch.heading_deg, m, out=raw[k:k + b])
+        if smooth:                                                              # copies: a forward may reuse its output buffers
+            frame = (heat, ori, batch.gt, batch.gt_ori, batch.heading_deg, m)
+            if kept is None:
+                kept = [torch.empty((n,) + tuple(f.shape[1:]), device=dev, dtype=f.dtype) for f in frame]
+            for table, f in zip(kept, frame):
+                table[k:k + b].copy_(f)
         for j in range(b):
             if starts[k + j]:
                 filt.reset()
@@ -376,9 +392,39 @@ def evaluate_sequence(forward_fn, batches, filt, shift_px, starts, metres_per_pi
                 filt.step(heat[j:j + 1], ori[j:j + 1], shifts[k + j:k + j + 1], rows_out=trk[k + j:k + j + 1])
             ops.eval_metrics(filt.belief, ori[j:j + 1], batch.gt[j:j + 1], batch.gt_ori[j:j + 1], batch.heading_deg[j:j + 1],
                              m[j:j + 1], out=fil[k + j:k + j + 1])
+            if smooth:
+                posts[k + j:k + j + 1].copy_(filt.belief)
         k += b
-    table = torch.cat([raw, fil, trk], dim=1).cpu().numpy()                      # the one read-back (and the one sync)
-    raw_rows, fil_rows, tracks = table[:, :12], table[:, 12:24], table[:, 24:]
+    tables = [raw, fil, trk]
+    if smooth:
+        tables += _smooth_sequence(filt, kept, posts, trk, motions if motion is not None else shifts, motion is not None, starts)
+    table = torch.cat(tables, dim=1).cpu().numpy()                               # the one read-back (and the one sync)
+    raw_rows, fil_rows, tracks = table[:, :12], table[:, 12:24], table[:, 24:38]
     masks = {name: np.isin(idx, np.asarray(sel)) for name, sel in sets.items()} if sets else None
-    return {"raw": summarise(raw_rows, masks), "filtered": summarise(fil_rows, masks), "tracks": tracks,
-            "raw_rows": raw_rows, "filtered_rows": fil_rows, "indices": idx}
+    res = {"raw": summarise(raw_rows, masks), "filtered": summarise(fil_rows, masks), "tracks": tracks,
+           "raw_rows": raw_rows, "filtered_rows": fil_rows, "indices": idx}
+    if smooth:
+        res["smoothed_rows"], res["smoothed_tracks"] = table[:, 38:50], table[:, 50:]
+        res["smoothed"] = summarise(res["smoothed_rows"], masks)
+    return res
+
+
+def _smooth_sequence(filt, kept, posts, filtered, move, rigid, starts):
+    """evaluate_sequence(smooth=True) after its loop: the backward pass of tracking.SequenceSmoother over the kept frames and
+    the filter's posteriors, and the protocol rows of every smoothed belief.  Returns device tables [n,12] and [n,14]."""
+    from . import ops, tracking
+    dev, n = posts.device, posts.shape[0]
+    sm = tracking.SequenceSmoother(filt.hw, filt.sigma_px, filt.radius, filt.outlier, dev)
+    heat, ori, gt, gt_ori, heading, m = kept
+    if rigid:
+        _, taps = tracking.motion_taps(torch.zeros((n, 2), device=dev, dtype=torch.float64), sm.sigma_px, sm.radius)
+        move = move.to(torch.float64).reshape(n, 6).contiguous()
+    else:
+        move, taps = tracking.motion_taps(move, sm.sigma_px, sm.radius)
+    reset = torch.as_tensor(starts.astype(np.int32)).to(dev)
+    out = sm.backward(heat, ori, move, taps, reset, posts, filtered, keep_beliefs=True)
+    rows = torch.empty((n, 12), device=dev, dtype=torch.float64)
+    for t in range(n):
+        ops.eval_metrics(out["beliefs"][t:t + 1], ori[t:t + 1], gt[t:t + 1], gt_ori[t:t + 1], heading[t:t + 1], m[t:t + 1],
+                         out=rows[t:t + 1])
+    return [rows, out["smoothed"]]

@@ -1027,6 +1027,78 @@ def _belief_step(who, entry, prior, heatmap, ori, move, move_name, move_dtype, m
     return out, post
 
 
+def belief_smooth_step(beta, heatmap, alpha, ori, offsets, taps, outlier=0.0, cut=None, beta_out=None, smooth=None, scratch=None,
+                       out=None):
+    """One backward step of the forward-backward smoother per track on the device (two launches;
+    ccvpe_amd.tracking.smooth_step_spec is the specification), for the pair of frames (s, t = s + 1): beta [B,1,h,w] the
+    backward message of frame t (any positive scale), heatmap [B,1,h,w] of frame t, alpha [B,1,h,w] the filter's posterior of
+    frame s, ori [B,2,h,w] of frame s; offsets [B,2] int32 and taps [B,2,2R+1] the FORWARD step's own of frame t — the kernel
+    applies the predict's adjoint (offsets the other way, taps reversed) itself.  cut [B] int32 or None: a non-zero entry marks
+    frame s as the last of its segment (frame t is a start, a filter reset, or does not exist): its smoothed belief is alpha
+    and the message restarts uniform.  beta_out, smooth: a caller's [B,1,h,w] tensors that overlap neither each other nor an
+    input; scratch: B * belief_partials(h, w) float64; out: a caller's [B,14] float64 slice.
+    Returns (rows [B,14] float64 — the columns of belief_step for the smoothed belief, RESET = the state, SURVIVED = sum B',
+    smooth, beta_out)."""
+    return _belief_smooth_step("belief_smooth_step", "ccvpe_belief_smooth_step_f32", beta, heatmap, alpha, ori, offsets, "offsets",
+                               torch.int32, 2, taps, outlier, cut, beta_out, smooth, scratch, out)
+
+
+def belief_smooth_step_rigid(beta, heatmap, alpha, ori, motion, taps, outlier=0.0, cut=None, beta_out=None, smooth=None,
+                             scratch=None, out=None):
+    """belief_smooth_step for a rigid motion of the grid (ccvpe_amd.tracking.smooth_step_rigid_spec is the specification):
+    `motion` [B,6] float64 on the device is the FORWARD rigid step's own rows of frame t (tracking.rigid_motion,
+    tracking.kitti_motions); the kernel inverts them (tracking.invert_motion) and resamples M beta along the reverse motion
+    before the reversed-tap blur.  Not the exact adjoint of the rigid predict — a bilinear gather's adjoint is a scatter — but
+    the same continuous model discretised the other way; equal to belief_smooth_step for angle 0 or quarter turns with
+    whole-pixel shifts.  Every other argument, every check and the return value are belief_smooth_step's."""
+    return _belief_smooth_step("belief_smooth_step_rigid", "ccvpe_belief_smooth_step_rigid_f32", beta, heatmap, alpha, ori, motion,
+                               "motion", torch.float64, 6, taps, outlier, cut, beta_out, smooth, scratch, out)
+
+
+def _belief_smooth_step(who, entry, beta, heatmap, alpha, ori, move, move_name, move_dtype, move_cols, taps, outlier, cut, beta_out,
+                        smooth, scratch, out):
+    lib = _lib.load()
+    for t, nm in ((beta, "beta"), (heatmap, "heatmap"), (alpha, "alpha"), (ori, "ori"), (taps, "taps"), (beta_out, "beta_out"),
+                  (smooth, "smooth")):
+        _chk(t, nm)
+    _chk(move, move_name, move_dtype)
+    _chk(cut, "cut", torch.int32)
+    for t, nm in ((scratch, "scratch"), (out, "out")):
+        _chk(t, nm, torch.float64)
+    if heatmap.dim() != 4 or heatmap.shape[1] != 1:
+        raise ValueError("%s: heatmap [B,1,h,w] expected, got %s" % (who, tuple(heatmap.shape)))
+    b, _, h, w = heatmap.shape
+    if beta.shape != heatmap.shape or alpha.shape != heatmap.shape or ori.shape != (b, 2, h, w):
+        raise ValueError("%s: beta and alpha [B,1,h,w] like heatmap and ori [B,2,h,w] expected" % who)
+    if taps.dim() != 3 or taps.shape[0] != b or taps.shape[1] != 2 or taps.shape[2] % 2 != 1:
+        raise ValueError("%s: taps must be [%d,2,2R+1], got %s" % (who, b, tuple(taps.shape)))
+    radius = (taps.shape[2] - 1) // 2
+    if tuple(move.shape) != (b, move_cols):
+        raise ValueError("%s: %s must be [%d,%d], got %s" % (who, move_name, b, move_cols, tuple(move.shape)))
+    if cut is not None and cut.numel() != b:
+        raise ValueError("%s: cut must hold one flag per track" % who)
+    need = b * belief_partials(h, w)
+    if scratch is None:
+        scratch = _empty((need,), device=heatmap.device, dtype=torch.float64)
+    elif scratch.numel() < need:
+        raise ValueError("%s: scratch holds %d doubles, %d needed" % (who, scratch.numel(), need))
+    maps = []
+    for t, nm in ((beta_out, "beta_out"), (smooth, "smooth")):
+        if t is None:
+            t = _empty(tuple(heatmap.shape), device=heatmap.device)
+        elif t.shape != heatmap.shape:
+            raise ValueError("%s: %s must be %s, got %s" % (who, nm, tuple(heatmap.shape), tuple(t.shape)))
+        maps.append(t)
+    beta_out, smooth = maps
+    if out is None:
+        out = _empty((b, 14), device=heatmap.device, dtype=torch.float64)
+    elif tuple(out.shape) != (b, 14):
+        raise ValueError("%s: out must be [%d,14], got %s" % (who, b, tuple(out.shape)))
+    check(getattr(lib, entry)(_ptr(beta), _ptr(heatmap), _ptr(alpha), _ptr(ori), _ptr(move), _ptr(taps), radius, float(outlier),
+                              _ptr(cut), _ptr(beta_out), _ptr(smooth), _ptr(scratch), _ptr(out), b, h, w, _stream()), entry)
+    return out, smooth, beta_out
+
+
 def _loss_common(fn, name, tensors, extra):
     lib = _lib.load()
     for i, t in enumerate(tensors):

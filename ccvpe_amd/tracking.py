@@ -20,7 +20,16 @@ map of `rigid_motion` and then blurred with centred taps — `step_rigid_spec` i
 device step, `HistogramFilter.step(motion=...)` the filter's entry and `kitti_motions` the per-frame motions of a KITTI test
 split.
 
-Out of scope: a change of scale between patch frames, learned motion models, bf16 beliefs.
+Offline — a recorded drive, evaluated after the fact — the estimate of frame t is the SMOOTHED one, given the whole drive:
+`SequenceSmoother` filters one track forward, keeps every posterior and walks back with the backward step
+
+    G = M_t beta_t,   B' = adjoint of the predict applied to G,   smooth_s = alpha_s B' / sum,   beta_s = B' / sum
+
+(`smooth_step_spec` / `smooth_step_rigid_spec` are the specifications, `ops.belief_smooth_step` / `ops.belief_smooth_step_rigid`
+the device steps, `invert_motion` the reverse of a rigid motion row); `evaluate.evaluate_sequence(..., smooth=True)` reports it.
+
+Out of scope: a change of scale between patch frames, learned motion models, bf16 beliefs; for the smoother also several
+tracks per `SequenceSmoother`, fixed-lag (online) smoothing and the most-likely-path (max-product) variant.
 """
 import math
 import os
@@ -228,19 +237,114 @@ def _step_spec(prior, heat, ori, predict, taps, outlier, reset, return_u):
         if state:
             u = m
             z = float(u.sum())
-        with np.errstate(divide="ignore", invalid="ignore"):
-            inv = np.float64(np.float32(np.float64(1.0) / np.float64(z)))
-            post[t] = (u * inv).astype(np.float32)
-            p = u / z
-            my, mx = float((p * yy).sum()), float((p * xx).sum())
-            var_yy, var_xx = float((p * (yy - my) ** 2).sum()), float((p * (xx - mx) ** 2).sum())
-            cov = float((p * (yy - my) * (xx - mx)).sum())
-        k = int(np.argmax(u.reshape(-1)))
-        py, px = divmod(k, w)
-        c, s = ori[t, 0, py, px], ori[t, 1, py, px]
-        rows[t] = (py, px, post[t, py, px], c, s, _angle_spec(c, s), z, state, my, mx, var_yy, var_xx, cov, survived)
+        post[t], rows[t] = _normalise_spec(u, z, ori[t], state, survived, yy, xx)
         us[t] = u
     return (post, rows, us) if return_u else (post, rows)
+
+
+def _normalise_spec(u, z, ori, state, survived, yy, xx):
+    """The end of a step, forward or backward: (u * float32(1 / z) stored as float32, the row read off u)."""
+    w = u.shape[1]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        inv = np.float64(np.float32(np.float64(1.0) / np.float64(z)))
+        post = (u * inv).astype(np.float32)
+        p = u / z
+        my, mx = float((p * yy).sum()), float((p * xx).sum())
+        var_yy, var_xx = float((p * (yy - my) ** 2).sum()), float((p * (xx - mx) ** 2).sum())
+        cov = float((p * (yy - my) * (xx - mx)).sum())
+    k = int(np.argmax(u.reshape(-1)))
+    py, px = divmod(k, w)
+    c, s = ori[0, py, px], ori[1, py, px]
+    return post, (py, px, post[py, px], c, s, _angle_spec(c, s), z, state, my, mx, var_yy, var_xx, cov, survived)
+
+
+def invert_motion(motion):
+    """The inverse of rigid-motion rows, [B,6] -> [B,6] float64: if a row maps (y, x) to (sy, sx), the result maps (sy, sx)
+    back to (y, x).  A general 2 x 2 inverse with every product, sum and quotient rounded on its own (the device does the
+    same operations in the same order): exact for the 0 / +-1 rotations `rigid_motion` produces with whole or half-pixel
+    translations.  A singular or non-finite row gives a row of NaN, which samples nothing."""
+    m = np.array(motion, dtype=np.float64).reshape(-1, 6)
+    a00, a01, a02, a10, a11, a12 = (m[:, k] for k in range(6))
+    with np.errstate(all="ignore"):
+        det = a00 * a11 - a01 * a10
+        b00, b01, b10, b11 = a11 / det, -a01 / det, -a10 / det, a00 / det
+        out = np.stack([b00, b01, -(b00 * a02 + b01 * a12), b10, b11, -(b10 * a02 + b11 * a12)], axis=1)
+    ok = np.isfinite(m).all(axis=1) & np.isfinite(det) & (det != 0)
+    out[~ok] = np.nan
+    return out
+
+
+def smooth_step_spec(beta, heat, alpha, ori, offsets, taps, outlier=0.0, cut=None, return_v=False):
+    """The specification of ccvpe_belief_smooth_step_f32 in numpy float64: one backward step of the forward-backward smoother
+    for the pair of frames (s, t = s + 1), one track at a time.  beta [B,h,w] or [B,1,h,w] float32 > 0: the backward message
+    of frame t at any scale; heat: the heat-map of frame t; alpha: the filter's posterior of frame s; ori [B,2,h,w] of frame
+    s; offsets [B,2] and taps [B,2,2R+1]: the FORWARD step's own inputs of frame t; cut [B] or None.
+
+    Measure: M = (1 - outlier) heat + outlier / (h w), G = M beta.  Back-predict, the exact adjoint of the forward predict:
+    B'[y,x] = sum_i ky[i+R] sum_j kx[j+R] G[y + oy + i, x + ox + j], G = 0 outside the grid (the forward predict with the
+    offsets negated and both tap vectors reversed).  V = alpha B', Z = sum V, S = sum B'.  State: 1 when cut[b] != 0 (frame s
+    is the last of its segment; the back-predict is skipped: S = 0), 2 when not (Z > 0 and finite and S > 0 and finite); then
+    V := alpha, Z := sum alpha and the message is float32(1 / (h w)) everywhere.  smooth = V * float32(1 / Z) and
+    beta_out = B' * float32(1 / S), stored as float32.  Row: the forward step's columns read off V — RESET holds the state,
+    SURVIVED holds S.  Returns (smooth float32 [B,h,w], beta_out float32 [B,h,w], rows float64 [B,14]) and, with return_v, V
+    float64 [B,h,w]."""
+    b = np.asarray(heat).shape[0]
+    offsets = np.asarray(offsets).reshape(b, 2)
+    return _smooth_step_spec(beta, heat, alpha, ori, lambda t, g, ky, kx: _predict_spec(g, -int(offsets[t, 0]), -int(offsets[t, 1]),
+                                                                                      ky[::-1], kx[::-1]),
+                             taps, outlier, cut, return_v)
+
+
+def smooth_step_rigid_spec(beta, heat, alpha, ori, motion, taps, outlier=0.0, cut=None, return_v=False):
+    """The specification of ccvpe_belief_smooth_step_rigid_f32: `smooth_step_spec` with the back-predict
+
+        B' = blur(warp(G; invert_motion(motion)), taps reversed)
+
+    where motion [B,6] is the FORWARD rigid step's own input of frame t and warp is `step_rigid_spec`'s bilinear rule.  This
+    is NOT the exact adjoint of the rigid predict — the adjoint of a bilinear gather is a scatter — but the same continuous
+    model discretised along the reverse motion: exact in the continuum, because the blur is isotropic and the motion has unit
+    Jacobian.  For angle 0 or quarter turns with whole-pixel shifts (and centred taps) it equals smooth_step_spec value for
+    value."""
+    b = np.asarray(heat).shape[0]
+    back = invert_motion(np.asarray(motion, dtype=np.float64).reshape(b, 6))
+    return _smooth_step_spec(beta, heat, alpha, ori,
+                             lambda t, g, ky, kx: _blur_spec(_warp_spec(g, back[t], (len(ky) - 1) // 2), ky[::-1], kx[::-1]),
+                             taps, outlier, cut, return_v)
+
+
+def _smooth_step_spec(beta, heat, alpha, ori, backpredict, taps, outlier, cut, return_v):
+    heat = np.asarray(heat, dtype=np.float32)
+    b, h, w = heat.shape[0], heat.shape[-2], heat.shape[-1]
+    heat = heat.reshape(b, h, w).astype(np.float64)
+    beta = np.asarray(beta, dtype=np.float32).reshape(b, h, w).astype(np.float64)
+    alpha = np.asarray(alpha, dtype=np.float32).reshape(b, h, w).astype(np.float64)
+    ori = np.asarray(ori, dtype=np.float32).reshape(b, 2, h, w)
+    taps = np.asarray(taps, dtype=np.float32).reshape(b, 2, -1)
+    a = np.float64(np.float32(outlier))
+    smooth, message = np.zeros((b, h, w), dtype=np.float32), np.zeros((b, h, w), dtype=np.float32)
+    vs = np.zeros((b, h, w), dtype=np.float64)
+    rows = np.full((b, 14), np.nan, dtype=np.float64)
+    yy, xx = np.mgrid[0:h, 0:w].astype(np.float64)
+    for t in range(b):
+        state, s = 0, 0.0
+        if cut is not None and int(np.asarray(cut).reshape(-1)[t]) != 0:
+            state = 1
+        else:
+            m = (1 - a) * heat[t] + a / (h * w)
+            bp = backpredict(t, m * beta[t], taps[t, 0], taps[t, 1])
+            v = alpha[t] * bp
+            z, s = float(v.sum()), float(bp.sum())
+            if not (z > 0 and np.isfinite(z) and s > 0 and np.isfinite(s)):
+                state = 2
+        if state:
+            v = alpha[t]
+            z = float(v.sum())
+            message[t] = np.float32(np.float64(1.0) / np.float64(h * w))
+        else:
+            message[t] = (bp * np.float64(np.float32(np.float64(1.0) / np.float64(s)))).astype(np.float32)
+        smooth[t], rows[t] = _normalise_spec(v, z, ori[t], state, s, yy, xx)
+        vs[t] = v
+    return (smooth, message, rows, vs) if return_v else (smooth, message, rows)
 
 
 class HistogramFilter(object):
@@ -324,6 +428,109 @@ class HistogramFilter(object):
         self._reset.zero_()
         self._cur = 1 - self._cur
         return rows
+
+
+class SequenceSmoother(object):
+    """The forward-backward smoother of ONE track over a recorded drive: the belief of frame t given the whole drive.
+
+    `run` filters the T frames forward (ops.belief_step / ops.belief_step_rigid, as HistogramFilter steps) and keeps every
+    posterior, then walks back with ops.belief_smooth_step / ops.belief_smooth_step_rigid: 2 launches per frame each way, no
+    read-back.  Memory: h w 4 bytes per frame for the posteriors (1 MB at 512 x 512), beside the caller's heat and ori; as
+    much again with keep_beliefs.  sigma_px, radius, outlier: as HistogramFilter (same ValueErrors).
+    Out of scope: several tracks per smoother, fixed-lag (online) smoothing, the most-likely-path (max-product) variant, bf16
+    maps, a change of scale between patch frames."""
+
+    def __init__(self, hw=(512, 512), sigma_px=1.0, radius=None, outlier=0.0, device="cuda"):
+        self.hw = (int(hw[0]), int(hw[1]))
+        if self.hw[0] <= 0 or self.hw[1] <= 0:
+            raise ValueError("hw must be positive")
+        self.sigma_px = float(sigma_px)
+        if not self.sigma_px >= 0:
+            raise ValueError("sigma_px must be >= 0")
+        self.radius = int(math.ceil(3 * self.sigma_px)) + 1 if radius is None else int(radius)
+        if not 0 <= self.radius <= MAX_RADIUS:
+            raise ValueError("radius %d outside [0, %d]: use a smaller sigma_px or pass radius" % (self.radius, MAX_RADIUS))
+        if not 0.0 <= float(outlier) <= 1.0:
+            raise ValueError("outlier must be in [0, 1]")
+        self.outlier, self.device = float(outlier), torch.device(device)
+
+    def run(self, heat, ori, shift_px=None, motion=None, starts=None, keep_beliefs=False):
+        """heat [T,1,h,w], ori [T,2,h,w] on the device, in drive order; exactly one of shift_px [T,2] = (dy, dx) and motion
+        [T,6] float64 (`rigid_motion` rows), the motion INTO each frame as HistogramFilter.step takes it (tensors on any device
+        or arrays; row 0 is not used); starts [T] marks frames where the filter restarts (frame 0 always does).
+        Returns {"filtered": rows [T,14] of the forward pass, "smoothed": rows [T,14] of the smoothed beliefs (RESET: 0 chained,
+        1 last frame of its segment, 2 the message died out; SURVIVED: the back-predicted mass), "beliefs": the smoothed
+        beliefs [T,1,h,w] with keep_beliefs, else None}, all on the device."""
+        if (shift_px is None) == (motion is None):
+            raise ValueError("run: pass exactly one of shift_px and motion")
+        if heat.dim() != 4 or tuple(heat.shape[1:]) != (1,) + self.hw or heat.shape[0] < 1:
+            raise ValueError("run: heat must be [T,1,%d,%d], got %s" % (self.hw + (tuple(heat.shape),)))
+        n = int(heat.shape[0])
+        if tuple(ori.shape) != (n, 2) + self.hw:
+            raise ValueError("run: ori must be [%d,2,%d,%d], got %s" % ((n,) + self.hw + (tuple(ori.shape),)))
+        dev = self.device
+        if motion is not None:
+            move = motion if torch.is_tensor(motion) else torch.from_numpy(np.array(motion, dtype=np.float64))
+            move = move.to(device=dev, dtype=torch.float64)
+            if move.numel() != 6 * n:
+                raise ValueError("run: motion must be [%d,6]" % n)
+            move = move.reshape(n, 6).contiguous()
+            _, taps = motion_taps(torch.zeros((n, 2), device=dev, dtype=torch.float64), self.sigma_px, self.radius)
+        else:
+            shift = torch.as_tensor(shift_px).to(dev)
+            if shift.numel() != 2 * n:
+                raise ValueError("run: shift_px must be [%d,2]" % n)
+            move, taps = motion_taps(shift, self.sigma_px, self.radius)
+        reset = torch.zeros((n,), device=dev, dtype=torch.int32)
+        if starts is not None:
+            st = torch.as_tensor(np.asarray(starts).reshape(-1).astype(np.int32))
+            if st.numel() != n:
+                raise ValueError("run: starts must hold one entry per frame (%d)" % n)
+            reset.copy_(st)
+        reset[0] = 1
+        alphas = self.forward(heat, ori, move, taps, reset)
+        return self.backward(heat, ori, move, taps, reset, alphas[0], alphas[1], keep_beliefs)
+
+    def _steps(self, rigid):
+        from . import ops
+        return (ops.belief_step_rigid, ops.belief_smooth_step_rigid) if rigid else (ops.belief_step, ops.belief_smooth_step)
+
+    def forward(self, heat, ori, move, taps, reset):
+        """The forward pass: every posterior written straight into a [T,1,h,w] table.  move: offsets int32 [T,2] or motion
+        float64 [T,6]; reset int32 [T].  Returns (posteriors, rows [T,14])."""
+        from . import ops
+        step = self._steps(move.dtype == torch.float64)[0]
+        n, (h, w) = int(heat.shape[0]), self.hw
+        table = torch.empty((n, 1, h, w), device=self.device, dtype=torch.float32)
+        rows = torch.empty((n, 14), device=self.device, dtype=torch.float64)
+        scratch = torch.empty((ops.belief_partials(h, w),), device=self.device, dtype=torch.float64)
+        first = table[n - 1:n] if n > 1 else torch.zeros((1, 1, h, w), device=self.device)      # frame 0 resets: not read
+        for t in range(n):
+            step(table[t - 1:t] if t else first, heat[t:t + 1], ori[t:t + 1], move[t:t + 1], taps[t:t + 1], outlier=self.outlier,
+                 reset=reset[t:t + 1], post=table[t:t + 1], scratch=scratch, out=rows[t:t + 1])
+        return table, rows
+
+    def backward(self, heat, ori, move, taps, reset, alphas, filtered, keep_beliefs=False):
+        """The backward pass over the posteriors `alphas` [T,1,h,w] and the forward rows `filtered` [T,14] of a forward pass
+        with the same inputs.  The cut flags are made on the device: frame t is the last of its segment when frame t + 1 is
+        a start, when the forward pass reset there (RESET != 0), or when there is no frame t + 1."""
+        from . import ops
+        back = self._steps(move.dtype == torch.float64)[1]
+        n, (h, w) = int(heat.shape[0]), self.hw
+        cut = torch.ones((n,), device=self.device, dtype=torch.int32)
+        if n > 1:
+            cut[:-1] = ((reset[1:] != 0) | (filtered[1:, RESET] != 0)).to(torch.int32)
+        rows = torch.empty((n, 14), device=self.device, dtype=torch.float64)
+        scratch = torch.empty((ops.belief_partials(h, w),), device=self.device, dtype=torch.float64)
+        beta = [torch.empty((1, 1, h, w), device=self.device, dtype=torch.float32) for _ in range(2)]
+        beliefs = torch.empty((n, 1, h, w), device=self.device, dtype=torch.float32) if keep_beliefs else None
+        one = None if keep_beliefs else torch.empty((1, 1, h, w), device=self.device, dtype=torch.float32)
+        for t in range(n - 1, -1, -1):
+            nxt = min(t + 1, n - 1)                                            # the last frame is cut: frame `nxt` is not read
+            back(beta[(t + 1) & 1], heat[nxt:nxt + 1], alphas[t:t + 1], ori[t:t + 1], move[nxt:nxt + 1], taps[nxt:nxt + 1],
+                 outlier=self.outlier, cut=cut[t:t + 1], beta_out=beta[t & 1], smooth=beliefs[t:t + 1] if keep_beliefs else one,
+                 scratch=scratch, out=rows[t:t + 1])
+        return {"filtered": filtered, "smoothed": rows, "beliefs": beliefs}
 
 
 def oxford_shifts(pairs, indices=None):
