@@ -134,6 +134,8 @@ PROTOTYPES = {
     "ccvpe_belief_step_rigid_f32": (c_int, [c_void_p] * 5 + [c_int, c_float] + [c_void_p] * 4 + [c_int] * 3 + [c_void_p]),
     "ccvpe_belief_smooth_step_f32": (c_int, [c_void_p] * 6 + [c_int, c_float] + [c_void_p] * 5 + [c_int] * 3 + [c_void_p]),
     "ccvpe_belief_smooth_step_rigid_f32": (c_int, [c_void_p] * 6 + [c_int, c_float] + [c_void_p] * 5 + [c_int] * 3 + [c_void_p]),
+    "ccvpe_belief_viterbi_step_f32": (c_int, [c_void_p] * 5 + [c_int, c_float] + [c_void_p] * 4 + [c_int] * 3 + [c_void_p]),
+    "ccvpe_belief_backtrack_f32": (c_int, [c_void_p] * 4 + [c_int] + [c_void_p] * 3 + [c_int] * 4 + [c_void_p]),
     "ccvpe_infonce_scratch_floats": (c_int, [c_int, c_int]),
     "ccvpe_infonce_loss_f32": (c_int, [c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "ccvpe_cross_entropy_loss_f32": (c_int, [c_void_p] * 4 + [c_int, c_int, c_void_p]),

@@ -23,6 +23,11 @@
 // the forward record with alpha in M's place.  Launch two, belief_smooth_finish_kernel: the shared record merge
 // (bf_merge_records), the state, BOTH maps scaled (or the fallback written), the shared row (bf_write_row).
 // What is not shared: the value a staged pixel takes (bf_src), the second output map and the two-map scaling loop.
+//
+// The most likely path (ccvpe_belief_viterbi_step_f32, ccvpe_belief_backtrack_f32; tracking.viterbi_step_spec / backtrack_spec):
+// belief_viterbi_kernel is the predict kernel with bf_passes in its max form (sums over taps become maxima) and launch two is
+// belief_finish_kernel; belief_backtrack_kernel walks a whole drive in one launch, a workgroup per track, and recomputes each
+// link's decision at the one pixel the path visits — there are no back-pointer maps.
 #include "common.h"
 
 namespace ccvpe {
@@ -129,8 +134,10 @@ __device__ __forceinline__ void bf_stage_shift(float* T, const float* __restrict
 }
 
 // The barrier after the staging of T, the row pass and the column pass: q[o] is the blurred value of tile pixel
-// (4 (tid / 64) + o, tid % 64).  REV indexes both tap vectors in reverse (the backward step's adjoint blur).
-template <bool REV>
+// (4 (tid / 64) + o, tid % 64).  REV indexes both tap vectors in reverse (the backward step's adjoint blur).  MAXP is the
+// max-product form (tracking.viterbi_step_spec): every sum over taps becomes a maximum, acc = fmaxf(acc, k * w) from a zero
+// start — a NaN product is ignored and negative values count as zero; staging, layout and barriers are the same.
+template <bool REV, bool MAXP = false>
 __device__ __forceinline__ void bf_passes(const float* T, float* mid, const float* __restrict__ taps, int R, bool skip, int b,
                                           float* q) {
   const int tid = threadIdx.x;
@@ -152,10 +159,10 @@ __device__ __forceinline__ void bf_passes(const float* T, float* mid, const floa
           const int j = 4 * m + jj;
           if (j < K) {
             const float k = kx[REV ? j : 2 * R - j];
-            a0 = fmaf(k, wv[jj], a0);
-            a1 = fmaf(k, wv[jj + 1], a1);
-            a2 = fmaf(k, wv[jj + 2], a2);
-            a3 = fmaf(k, wv[jj + 3], a3);
+            a0 = MAXP ? fmaxf(a0, __fmul_rn(k, wv[jj])) : fmaf(k, wv[jj], a0);
+            a1 = MAXP ? fmaxf(a1, __fmul_rn(k, wv[jj + 1])) : fmaf(k, wv[jj + 1], a1);
+            a2 = MAXP ? fmaxf(a2, __fmul_rn(k, wv[jj + 2])) : fmaf(k, wv[jj + 2], a2);
+            a3 = MAXP ? fmaxf(a3, __fmul_rn(k, wv[jj + 3])) : fmaf(k, wv[jj + 3], a3);
           }
         }
         cur = nxt;
@@ -174,10 +181,10 @@ __device__ __forceinline__ void bf_passes(const float* T, float* mid, const floa
     for (int i = 0; i < K; ++i) {
       const float w3 = mc[(i + 3) * BF_TW];
       const float k = ky[REV ? i : 2 * R - i];
-      q[0] = fmaf(k, w0, q[0]);
-      q[1] = fmaf(k, w1, q[1]);
-      q[2] = fmaf(k, w2, q[2]);
-      q[3] = fmaf(k, w3, q[3]);
+      q[0] = MAXP ? fmaxf(q[0], __fmul_rn(k, w0)) : fmaf(k, w0, q[0]);
+      q[1] = MAXP ? fmaxf(q[1], __fmul_rn(k, w1)) : fmaf(k, w1, q[1]);
+      q[2] = MAXP ? fmaxf(q[2], __fmul_rn(k, w2)) : fmaf(k, w2, q[2]);
+      q[3] = MAXP ? fmaxf(q[3], __fmul_rn(k, w3)) : fmaf(k, w3, q[3]);
       w0 = w1; w1 = w2; w2 = w3;
     }
   }
@@ -283,6 +290,118 @@ __global__ __launch_bounds__(256) void belief_predict_kernel(const float* __rest
                                (long long)x0 - R - ox, rows, PW, h, w);
   }
   bf_blur_measure(T, mid, heat, taps, R, one_minus_a, floor_m, skip, post, scratch, b, tile, ntiles, y0, x0, h, w);
+}
+
+// Launch one of the max-product step (tracking.viterbi_step_spec): the predict kernel with the passes in their max form,
+// P[y,x] = max_i ky[i+R] max_j kx[j+R] delta[y - oy - i, x - ox - j].  Every product is rounded once and a maximum rounds
+// nothing, so P carries the bits of __fmul_rn(ky, __fmul_rn(kx, delta)) at its winning source pixel — what
+// belief_backtrack_kernel recomputes.  Launch two is belief_finish_kernel: the map is normalised by its sum.
+template <bool VEC>
+__global__ __launch_bounds__(256) void belief_viterbi_kernel(const float* __restrict__ prior, const float* __restrict__ heat,
+                                                             const int* __restrict__ offsets, const float* __restrict__ taps,
+                                                             int R, float one_minus_a, float floor_m,
+                                                             const int* __restrict__ reset, float* __restrict__ post,
+                                                             double* __restrict__ scratch, int h, int w, int ntx, int nty) {
+  extern __shared__ cc_f32x4 bf_smem[];
+  const int ntiles = ntx * nty;
+  const int b = blockIdx.x / ntiles, tile = blockIdx.x - b * ntiles;
+  const int y0 = (tile / ntx) * BF_TH, x0 = (tile % ntx) * BF_TW;
+  const int rows = BF_TH + 2 * R, PW = bf_pitch(R);
+  float* T = reinterpret_cast<float*>(bf_smem);
+  float* mid = T + rows * PW;
+  const bool skip = reset != nullptr && reset[b] != 0;
+  if (!skip) {
+    const long long oy = offsets[2 * b], ox = offsets[2 * b + 1];
+    bf_stage_shift<VEC, false>(T, prior + (size_t)b * h * w, nullptr, one_minus_a, floor_m, (long long)y0 - R - oy,
+                               (long long)x0 - R - ox, rows, PW, h, w);
+  }
+  float q[4];
+  bf_passes<false, true>(T, mid, taps, R, skip, b, q);
+  bf_epilogue<false>(q, heat, one_minus_a, floor_m, skip, post, nullptr, scratch, b, tile, ntiles, y0, x0, h, w);
+}
+
+// The most likely path of every track over a whole drive (tracking.backtrack_spec), one launch: a workgroup owns a track and
+// walks the frames from the last to the first.  There are no back-pointer maps — the decision of a link is recomputed at the
+// one pixel the path passes through: the lanes stride over the (2R+1)^2 source pixels of the current pixel, form
+// ky (kx delta) in the forward kernel's association and merge (value first, then the smaller flat source index).  Only
+// positive finite candidates compete.  deltas [T,B,h w], ori [T,B,2,h w], offsets [T,B,2], taps [T,B,2,2R+1], rows [T,B,14]
+// of the forward pass, reset [T,B] or null, path [T,B,8].  Pixels read from `rows` are clamped to the grid.
+constexpr int BF_PATH = 8;
+__global__ __launch_bounds__(256) void belief_backtrack_kernel(const float* __restrict__ deltas, const float* __restrict__ ori,
+                                                               const int* __restrict__ offsets, const float* __restrict__ taps,
+                                                               int R, const double* __restrict__ rows,
+                                                               const int* __restrict__ reset, double* __restrict__ path,
+                                                               int frames, int batch, int h, int w) {
+  __shared__ int cur[3];                                         // y, x, link of the frame being written
+  __shared__ float cur_score;
+  __shared__ float rv[4];
+  __shared__ int ri[4];
+  const int tid = threadIdx.x, b = blockIdx.x;
+  const int K = 2 * R + 1;
+  const size_t n = (size_t)h * w;
+  auto row_pixel = [&](int t, int* y, int* x) {                  // the arg-max of frame t's row, clamped (NaN gives 0)
+    const double* r = rows + ((size_t)t * batch + b) * 14;
+    const double ry = r[0], rx = r[1];
+    *y = ry >= 0.0 ? (ry < (double)h ? (int)ry : h - 1) : 0;
+    *x = rx >= 0.0 ? (rx < (double)w ? (int)rx : w - 1) : 0;
+  };
+  if (tid == 0) {
+    int y, x;
+    row_pixel(frames - 1, &y, &x);
+    cur[0] = y; cur[1] = x; cur[2] = 1;
+    cur_score = 0.f;
+  }
+  __syncthreads();
+  for (int t = frames - 1; t >= 0; --t) {
+    const int y = cur[0], x = cur[1];
+    const size_t tb = (size_t)t * batch + b;
+    if (tid == 0) {
+      const size_t e = (size_t)y * w + x;
+      const float c = ori[(tb * 2 + 0) * n + e], s = ori[(tb * 2 + 1) * n + e];
+      double ang = NAN;
+      if (fabsf(c) <= 1.0f && fabsf(s) <= 1.0f) ang = angle_deg_f64((double)c, s < 0.0f);
+      double* p = path + tb * BF_PATH;
+      p[0] = (double)y; p[1] = (double)x;
+      p[2] = (double)deltas[tb * n + e];
+      p[3] = (double)c; p[4] = (double)s; p[5] = ang;
+      p[6] = (double)cur[2]; p[7] = (double)cur_score;
+    }
+    if (t == 0) break;
+    const bool start = (reset != nullptr && reset[tb] != 0) || rows[tb * 14 + 7] != 0.0;      // uniform over the workgroup
+    BfArg best = {-INFINITY, BF_NONE};
+    if (!start) {
+      const long long cy = (long long)y - offsets[2 * tb], cx = (long long)x - offsets[2 * tb + 1];
+      const float* ky = taps + tb * 2 * K;
+      const float* kx = ky + K;
+      const float* dp = deltas + (tb - batch) * n;               // frame t - 1
+      for (int c = tid; c < K * K; c += 256) {
+        const int ii = c / K, jj = c - ii * K;
+        const long long sy = cy - (ii - R), sx = cx - (jj - R);
+        if (sy >= 0 && sy < h && sx >= 0 && sx < w) {
+          const int e = (int)(sy * w + sx);
+          const float v = __fmul_rn(ky[ii], __fmul_rn(kx[jj], dp[e]));
+          if (v > 0.f && v < INFINITY) best.merge(v, e);
+        }
+      }
+    }
+    best.wave_merge();
+    if ((tid & 63) == 0) { rv[tid >> 6] = best.v; ri[tid >> 6] = best.i; }
+    __syncthreads();                                             // every lane has read cur; the waves' candidates are in LDS
+    if (tid == 0) {
+#pragma unroll
+      for (int k = 1; k < 4; ++k) best.merge(rv[k], ri[k]);
+      if (best.i != BF_NONE) {
+        cur[0] = best.i / w; cur[1] = best.i % w; cur[2] = 0;
+        cur_score = best.v;
+      } else {
+        int py, px;
+        row_pixel(t - 1, &py, &px);
+        cur[0] = py; cur[1] = px; cur[2] = start ? 1 : 2;
+        cur_score = 0.f;
+      }
+    }
+    __syncthreads();
+  }
 }
 
 // Launch one of the backward step (tracking.smooth_step_spec): the forward step's own offsets and taps, used the other way
@@ -820,4 +939,62 @@ extern "C" int ccvpe_belief_smooth_step_rigid_f32(const float* beta, const float
                      one_minus_a, floor_m, cut, beta_out, smooth, scratch, h, w, ntx, nty);
   if (int rc = check_launch("belief_smooth_rigid_kernel")) return rc;
   return bf_smooth_finish(alpha, ori, cut, beta_out, smooth, scratch, rows, batch, h, w, ntiles, st);
+}
+
+extern "C" int ccvpe_belief_viterbi_step_f32(const float* prior, const float* heat, const float* ori, const int* offsets,
+                                             const float* taps, int radius, float outlier, const int* reset, float* post,
+                                             double* scratch, double* rows, int batch, int h, int w, void* stream) {
+  const char* who = "belief_viterbi_step";
+  int ntx, nty;
+  if (int rc = bf_check(who, prior, heat, ori, offsets, taps, radius, outlier, reset, post, scratch, rows, batch, h, w, &ntx, &nty))
+    return rc;
+  const long long ntiles = (long long)ntx * nty;
+  const size_t n = (size_t)h * w;
+  hipStream_t st = (hipStream_t)stream;
+  const float one_minus_a = 1.0f - outlier, floor_m = outlier / (float)n;
+  const int smem = (int)sizeof(float) * (BF_TH + 2 * radius) * (bf_pitch(radius) + BF_TW);
+  const bool vec1 = (w % 4) == 0 && aligned16(prior);
+  const dim3 grid1((unsigned)(ntiles * batch));
+  if (vec1) {
+    auto kern = belief_viterbi_kernel<true>;
+    static DevCache lds_set;
+    if (int rc = ensure_dyn_lds(lds_set, kern, smem, who)) return rc;
+    hipLaunchKernelGGL(kern, grid1, dim3(256), smem, st, prior, heat, offsets, taps, radius, one_minus_a, floor_m, reset, post,
+                       scratch, h, w, ntx, nty);
+  } else {
+    auto kern = belief_viterbi_kernel<false>;
+    static DevCache lds_set;
+    if (int rc = ensure_dyn_lds(lds_set, kern, smem, who)) return rc;
+    hipLaunchKernelGGL(kern, grid1, dim3(256), smem, st, prior, heat, offsets, taps, radius, one_minus_a, floor_m, reset, post,
+                       scratch, h, w, ntx, nty);
+  }
+  if (int rc = check_launch("belief_viterbi_kernel")) return rc;
+  return bf_finish(heat, ori, one_minus_a, floor_m, reset, post, scratch, rows, batch, h, w, ntiles, st);
+}
+
+extern "C" int ccvpe_belief_backtrack_f32(const float* deltas, const float* ori, const int* offsets, const float* taps, int radius,
+                                          const double* rows, const int* reset, double* path, int frames, int batch, int h, int w,
+                                          void* stream) {
+  const char* who = "belief_backtrack";
+  int ntx, nty;
+  if (frames <= 0 || batch <= 0 || !bf_tiles(h, w, &ntx, &nty)) return fail(CCVPE_EINVAL, "%s: bad shape", who);
+  if ((long long)frames * batch > 0x7fffffffLL) return fail(CCVPE_EINVAL, "%s: frames x batch > 2^31", who);
+  if (radius < 0 || radius > 32) return fail(CCVPE_EINVAL, "%s: radius %d outside [0, 32]", who, radius);
+  if (!deltas || !ori || !offsets || !taps || !rows || !path) return fail(CCVPE_EINVAL, "%s: null pointer", who);
+  if ((reinterpret_cast<uintptr_t>(rows) | reinterpret_cast<uintptr_t>(path)) & 7)
+    return fail(CCVPE_EINVAL, "%s: rows and path must be 8-byte aligned", who);
+  if ((reinterpret_cast<uintptr_t>(deltas) | reinterpret_cast<uintptr_t>(ori) | reinterpret_cast<uintptr_t>(offsets) |
+       reinterpret_cast<uintptr_t>(taps) | reinterpret_cast<uintptr_t>(reset)) & 3)
+    return fail(CCVPE_EINVAL, "%s: float and int arrays must be 4-byte aligned", who);
+  const size_t tb = (size_t)frames * batch, maps = tb * (size_t)h * w * sizeof(float), out = tb * BF_PATH * sizeof(double);
+  if (bf_overlap(deltas, maps, path, out)) return fail(CCVPE_EINVAL, "%s: deltas and path overlap", who);
+  if (bf_overlap(ori, 2 * maps, path, out)) return fail(CCVPE_EINVAL, "%s: ori and path overlap", who);
+  if (bf_overlap(rows, tb * 14 * sizeof(double), path, out)) return fail(CCVPE_EINVAL, "%s: rows and path overlap", who);
+  if (bf_overlap(offsets, tb * 2 * sizeof(int), path, out)) return fail(CCVPE_EINVAL, "%s: offsets and path overlap", who);
+  if (bf_overlap(taps, tb * 2 * (2 * (size_t)radius + 1) * sizeof(float), path, out))
+    return fail(CCVPE_EINVAL, "%s: taps and path overlap", who);
+  if (reset && bf_overlap(reset, tb * sizeof(int), path, out)) return fail(CCVPE_EINVAL, "%s: reset and path overlap", who);
+  hipLaunchKernelGGL(belief_backtrack_kernel, dim3((unsigned)batch), dim3(256), 0, (hipStream_t)stream, deltas, ori, offsets, taps,
+                     radius, rows, reset, path, frames, batch, h, w);
+  return check_launch("belief_backtrack_kernel");
 }

@@ -314,7 +314,8 @@ def evaluate_batches(forward_fn, batches, metres_per_pixel=None, sets=None):
     return res
 
 
-def evaluate_sequence(forward_fn, batches, filt, shift_px, starts, metres_per_pixel=None, sets=None, motion=None, smooth=False):
+def evaluate_sequence(forward_fn, batches, filt, shift_px, starts, metres_per_pixel=None, sets=None, motion=None, smooth=False,
+                      path=False):
     """The reference's test protocol along a drive, for the raw heat-maps AND for the belief of a histogram filter
     (ccvpe_amd.tracking.HistogramFilter with one track).  `batches`: a DeviceBatches in drive order — unshuffled, one rank,
     targets=True (ValueError otherwise); shift_px [n,2] and starts [n] per sample of `batches.indices`, e.g. from
@@ -332,8 +333,17 @@ def evaluate_sequence(forward_fn, batches, filt, shift_px, starts, metres_per_pi
     per frame at 512 x 512, and the smoothed beliefs (1 MB per frame) during the backward pass.  After the loop: the backward
     pass (two launches per frame) and one ccvpe_eval_metrics_f32 launch per smoothed belief; still ONE read-back.  The result
     gains "smoothed": summarise(...), "smoothed_rows": [n,12] and "smoothed_tracks": [n,14] (RESET holds the backward state).
-    With smooth=False the returned dict and the launches are exactly those described above."""
+    With smooth=False the returned dict and the launches are exactly those described above.
+
+    path=True adds the most likely path (tracking.MostLikelyPath with the filter's settings: ONE trajectory, the jointly most
+    likely sequence of grid cells; shift_px only — the rigid form is out of scope, ValueError with motion).  The loop keeps the
+    frames as smooth=True does; after it come the max-product forward pass (two launches per frame), one backtrack launch and
+    the protocol rows of a one-hot map at every path pixel (written on the device, no sync); still ONE read-back.  The result
+    gains "path": summarise(...), "path_rows": [n,12] and "path_tracks": [n,8] (tracking.PATH_Y ... PATH_SCORE).  With
+    path=False the returned dict and the launches are exactly those described above."""
     from . import ops
+    if path and motion is not None:
+        raise ValueError("evaluate_sequence: path=True takes shift_px; the most likely path under a rigid motion is out of scope")
     if not batches.targets:
         raise ValueError("evaluate_sequence needs DeviceBatches(..., targets=True): the ground truth comes from the batch")
     world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
@@ -377,7 +387,7 @@ def evaluate_sequence(forward_fn, batches, filt, shift_px, starts, metres_per_pi
              else mpp_const[:b])
         heat, ori = out[1], out[2]
         ops.eval_metrics(heat, ori, batch.gt, batch.gt_ori, batch.heading_deg, m, out=raw[k:k + b])
-        if smooth:                                                              # copies: a forward may reuse its output buffers
+        if smooth or path:                                                      # copies: a forward may reuse its output buffers
             frame = (heat, ori, batch.gt, batch.gt_ori, batch.heading_deg, m)
             if kept is None:
                 kept = [torch.empty((n,) + tuple(f.shape[1:]), device=dev, dtype=f.dtype) for f in frame]
@@ -398,15 +408,42 @@ def evaluate_sequence(forward_fn, batches, filt, shift_px, starts, metres_per_pi
     tables = [raw, fil, trk]
     if smooth:
         tables += _smooth_sequence(filt, kept, posts, trk, motions if motion is not None else shifts, motion is not None, starts)
+    if path:
+        tables += _path_sequence(filt, kept, shifts, starts)
     table = torch.cat(tables, dim=1).cpu().numpy()                               # the one read-back (and the one sync)
     raw_rows, fil_rows, tracks = table[:, :12], table[:, 12:24], table[:, 24:38]
     masks = {name: np.isin(idx, np.asarray(sel)) for name, sel in sets.items()} if sets else None
     res = {"raw": summarise(raw_rows, masks), "filtered": summarise(fil_rows, masks), "tracks": tracks,
            "raw_rows": raw_rows, "filtered_rows": fil_rows, "indices": idx}
     if smooth:
-        res["smoothed_rows"], res["smoothed_tracks"] = table[:, 38:50], table[:, 50:]
+        res["smoothed_rows"], res["smoothed_tracks"] = table[:, 38:50], table[:, 50:64]
         res["smoothed"] = summarise(res["smoothed_rows"], masks)
+    if path:
+        c = 64 if smooth else 38
+        res["path_rows"], res["path_tracks"] = table[:, c:c + 12], table[:, c + 12:c + 20]
+        res["path"] = summarise(res["path_rows"], masks)
     return res
+
+
+def _path_sequence(filt, kept, shifts, starts, chunk=64):
+    """evaluate_sequence(path=True) after its loop: tracking.MostLikelyPath over the kept frames and the protocol rows of a
+    one-hot map at every path pixel, `chunk` frames per ccvpe_eval_metrics_f32 launch.  The one-hot maps are written on the
+    device from the path table (no sync).  Returns device tables [n,12] and [n,8]."""
+    from . import ops, tracking
+    heat, ori, gt, gt_ori, heading, m = kept
+    dev, n = heat.device, heat.shape[0]
+    h, w = filt.hw
+    out = tracking.MostLikelyPath(filt.hw, filt.sigma_px, filt.radius, filt.outlier, dev).run(heat, ori, shifts, starts)
+    track = out["path"].reshape(n, 8)
+    pixel = (track[:, tracking.PATH_Y] * w + track[:, tracking.PATH_X]).to(torch.int64).reshape(n, 1)
+    rows = torch.empty((n, 12), device=dev, dtype=torch.float64)
+    onehot = torch.empty((min(n, chunk), 1, h, w), device=dev, dtype=torch.float32)
+    for k in range(0, n, chunk):
+        b = min(chunk, n - k)
+        onehot[:b].zero_()
+        onehot[:b].reshape(b, h * w).scatter_(1, pixel[k:k + b], 1.0)
+        ops.eval_metrics(onehot[:b], ori[k:k + b], gt[k:k + b], gt_ori[k:k + b], heading[k:k + b], m[k:k + b], out=rows[k:k + b])
+    return [rows, track]
 
 
 def _smooth_sequence(filt, kept, posts, filtered, move, rigid, starts):

@@ -989,6 +989,53 @@ def belief_step_rigid(prior, heatmap, ori, motion, taps, outlier=0.0, reset=None
                         taps, outlier, reset, post, scratch, out)
 
 
+def belief_viterbi_step(prior, heatmap, ori, offsets, taps, outlier=0.0, reset=None, post=None, scratch=None, out=None):
+    """belief_step in its max-product form (ccvpe_amd.tracking.viterbi_step_spec is the specification): the sums of the
+    predict become maxima, P[y,x] = max_i ky max_j kx prior[y - oy - i, x - ox - j]; the measure, the normalisation by the
+    map's SUM, the reset rules and the 14 columns are belief_step's (SURVIVED = sum P).  The forward pass of the most likely
+    path (tracking.MostLikelyPath).  Every argument, every check and the return value are belief_step's."""
+    return _belief_step("belief_viterbi_step", "ccvpe_belief_viterbi_step_f32", prior, heatmap, ori, offsets, "offsets", torch.int32,
+                        2, taps, outlier, reset, post, scratch, out)
+
+
+def belief_backtrack(deltas, ori, offsets, taps, rows, reset=None, out=None):
+    """The most likely path of every track over a whole drive in ONE launch (ccvpe_amd.tracking.backtrack_spec is the
+    specification): deltas [T,B,1,h,w] or [T,B,h,w] the posts of a belief_viterbi_step forward pass, ori [T,B,2,h,w], offsets
+    [T,B,2] int32 and taps [T,B,2,2R+1] the motion INTO each frame, rows [T,B,14] float64 the forward rows, reset [T,B] int32 or
+    None (frame 0 always starts a segment).  out: a caller's [T,B,8] float64 tensor.
+    Returns path [T,B,8] float64 — columns ccvpe_amd.tracking.PATH_Y ... PATH_SCORE."""
+    lib = _lib.load()
+    for t, nm in ((deltas, "deltas"), (ori, "ori"), (taps, "taps")):
+        _chk(t, nm)
+    _chk(offsets, "offsets", torch.int32)
+    _chk(reset, "reset", torch.int32)
+    for t, nm in ((rows, "rows"), (out, "out")):
+        _chk(t, nm, torch.float64)
+    if deltas.dim() == 5 and deltas.shape[2] == 1:
+        deltas = deltas.reshape(deltas.shape[0], deltas.shape[1], deltas.shape[3], deltas.shape[4])
+    if deltas.dim() != 4:
+        raise ValueError("belief_backtrack: deltas [T,B,h,w] or [T,B,1,h,w] expected, got %s" % (tuple(deltas.shape),))
+    n, b, h, w = deltas.shape
+    if tuple(ori.shape) != (n, b, 2, h, w):
+        raise ValueError("belief_backtrack: ori must be [%d,%d,2,%d,%d], got %s" % (n, b, h, w, tuple(ori.shape)))
+    if taps.dim() != 4 or tuple(taps.shape[:3]) != (n, b, 2) or taps.shape[3] % 2 != 1:
+        raise ValueError("belief_backtrack: taps must be [%d,%d,2,2R+1], got %s" % (n, b, tuple(taps.shape)))
+    radius = (taps.shape[3] - 1) // 2
+    if tuple(offsets.shape) != (n, b, 2):
+        raise ValueError("belief_backtrack: offsets must be [%d,%d,2], got %s" % (n, b, tuple(offsets.shape)))
+    if tuple(rows.shape) != (n, b, 14):
+        raise ValueError("belief_backtrack: rows must be [%d,%d,14], got %s" % (n, b, tuple(rows.shape)))
+    if reset is not None and tuple(reset.shape) != (n, b):
+        raise ValueError("belief_backtrack: reset must be [%d,%d], got %s" % (n, b, tuple(reset.shape)))
+    if out is None:
+        out = _empty((n, b, 8), device=deltas.device, dtype=torch.float64)
+    elif tuple(out.shape) != (n, b, 8):
+        raise ValueError("belief_backtrack: out must be [%d,%d,8], got %s" % (n, b, tuple(out.shape)))
+    check(lib.ccvpe_belief_backtrack_f32(_ptr(deltas), _ptr(ori), _ptr(offsets), _ptr(taps), radius, _ptr(rows), _ptr(reset),
+                                         _ptr(out), n, b, h, w, _stream()), "ccvpe_belief_backtrack_f32")
+    return out
+
+
 def _belief_step(who, entry, prior, heatmap, ori, move, move_name, move_dtype, move_cols, taps, outlier, reset, post, scratch, out):
     lib = _lib.load()
     for t, nm in ((prior, "prior"), (heatmap, "heatmap"), (ori, "ori"), (taps, "taps"), (post, "post")):

@@ -28,8 +28,16 @@ Offline — a recorded drive, evaluated after the fact — the estimate of frame
 (`smooth_step_spec` / `smooth_step_rigid_spec` are the specifications, `ops.belief_smooth_step` / `ops.belief_smooth_step_rigid`
 the device steps, `invert_motion` the reverse of a rigid motion row); `evaluate.evaluate_sequence(..., smooth=True)` reports it.
 
+One trajectory — the jointly most likely sequence of grid cells, which the per-frame arg-max of the smoothed marginals is
+not — is the max-product (Viterbi) solution: `MostLikelyPath` runs the forward step with the predict's sums replaced by maxima
+(`viterbi_step_spec`, `ops.belief_viterbi_step`) and keeps every map, then walks back in one launch (`backtrack_spec`,
+`ops.belief_backtrack`), recomputing each link's decision at the one pixel the path visits; there are no back-pointer maps.
+`evaluate.evaluate_sequence(..., path=True)` reports it.
+
 Out of scope: a change of scale between patch frames, learned motion models, bf16 beliefs; for the smoother also several
-tracks per `SequenceSmoother`, fixed-lag (online) smoothing and the most-likely-path (max-product) variant.
+tracks per `SequenceSmoother` and fixed-lag (online) smoothing; for the path the rigid (KITTI) form — its warp is a bilinear mix,
+not a maximum, so its back-pointer needs a definition of its own — stored back-pointer maps, log-domain maps, bf16 maps and
+fixed-lag decoding.
 """
 import math
 import os
@@ -39,6 +47,8 @@ import torch
 
 # columns of a track row (ccvpe_belief_step_f32 / step_spec)
 (PRED_Y, PRED_X, PROB, COS, SIN, ANGLE, EVIDENCE, RESET, MEAN_Y, MEAN_X, VAR_YY, VAR_XX, COV_YX, SURVIVED) = range(14)
+# columns of a path row (ccvpe_belief_backtrack_f32 / backtrack_spec)
+(PATH_Y, PATH_X, PATH_PROB, PATH_COS, PATH_SIN, PATH_ANGLE, PATH_LINK, PATH_SCORE) = range(8)
 MAX_RADIUS = 32
 
 
@@ -85,8 +95,11 @@ def motion_taps(shift_px, sigma_px, radius):
 
 
 def _predict_spec(prior, oy, ox, ky, kx):
+    return _blur_spec(_moved_spec(prior, oy, ox, (len(ky) - 1) // 2), ky, kx)
+
+
+def _moved_spec(prior, oy, ox, r):
     h, w = prior.shape
-    r = (len(ky) - 1) // 2
     # pad[r + y, r + x] = prior[y - oy, x - ox] for y in [-r, h + r): the prior is zero outside ITS grid, the moved prior is
     # not cropped before the blur (mass is lost only where it ends up off the grid)
     pad = np.zeros((h + 2 * r, w + 2 * r), dtype=np.float64)
@@ -94,7 +107,22 @@ def _predict_spec(prior, oy, ox, ky, kx):
     vy, vx = (ys >= 0) & (ys < h), (xs >= 0) & (xs < w)
     if vy.any() and vx.any():
         pad[np.ix_(vy, vx)] = prior[np.ix_(ys[vy], xs[vx])]
-    return _blur_spec(pad, ky, kx)
+    return pad
+
+
+def _maxblur_spec(pad, ky, kx):
+    """_blur_spec with every sum replaced by a maximum from a zero start, the same separable order; np.fmax ignores a NaN
+    candidate, as fmaxf does on the device."""
+    r = (len(ky) - 1) // 2
+    h, w = pad.shape[0] - 2 * r, pad.shape[1] - 2 * r
+    row = np.zeros((h + 2 * r, w), dtype=np.float64)
+    out = np.zeros((h, w), dtype=np.float64)
+    with np.errstate(invalid="ignore"):
+        for j in range(-r, r + 1):
+            row = np.fmax(row, np.float64(kx[j + r]) * pad[:, r - j:r - j + w])
+        for i in range(-r, r + 1):
+            out = np.fmax(out, np.float64(ky[i + r]) * row[r - i:r - i + h, :])
+    return out
 
 
 def _blur_spec(pad, ky, kx):
@@ -133,6 +161,89 @@ def step_spec(prior, heat, ori, offsets, taps, outlier=0.0, reset=None, return_u
     offsets = np.asarray(offsets).reshape(b, 2)
     return _step_spec(prior, heat, ori, lambda t, p, ky, kx: _predict_spec(p, offsets[t, 0], offsets[t, 1], ky, kx), taps,
                       outlier, reset, return_u)
+
+
+def viterbi_step_spec(prev, heat, ori, offsets, taps, outlier=0.0, reset=None, return_u=False):
+    """The specification of ccvpe_belief_viterbi_step_f32: `step_spec` with the sums of the predict replaced by maxima,
+
+        row[r,x] = max(0, max_j kx[j+R] pad[r, x - j]),   P[y,x] = max(0, max_i ky[i+R] row[y - i, x])
+
+    with pad the previous map moved by (oy, ox), zero outside its grid — P[y,x] is the best ky[i+R] kx[j+R] prev[y - oy - i,
+    x - ox - j].  Everything after the predict is step_spec's: M, U = P M, Z = sum U, the reset states, post = U * float32(1 / Z)
+    and the 14 columns (SURVIVED = sum P).  The map is normalised by its SUM, not its peak: the peak of post stays at or above
+    1 / (h w), so the recursion cannot underflow.  A NaN candidate is ignored and negative inputs count as zero."""
+    b = np.asarray(heat).shape[0]
+    offsets = np.asarray(offsets).reshape(b, 2)
+    return _step_spec(prev, heat, ori,
+                      lambda t, p, ky, kx: _maxblur_spec(_moved_spec(p, offsets[t, 0], offsets[t, 1], (len(ky) - 1) // 2), ky, kx),
+                      taps, outlier, reset, return_u)
+
+
+def backtrack_spec(deltas, ori, offsets, taps, rows, reset=None, return_margin=False):
+    """The specification of ccvpe_belief_backtrack_f32 in numpy float64: the most likely path through the maps of a
+    viterbi_step_spec forward pass.  deltas [T,B,h,w] float32 (the posts), ori [T,B,2,h,w], offsets [T,B,2] and taps
+    [T,B,2,2R+1] (the motion INTO each frame), rows [T,B,14] (the forward rows), reset [T,B] or None (frame 0 always counts
+    as set).  Returns path float64 [T,B,8], columns PATH_Y ... PATH_SCORE.
+
+    Per track, from t = T-1 down: frame T-1 takes its row's (PRED_Y, PRED_X), LINK 1.  For t >= 1, when reset[t] != 0 or
+    rows[t, RESET] != 0 frame t is a segment start and frame t-1 takes its row's arg-max, LINK 1.  Otherwise the candidates
+    are the source pixels (sy, sx) = (y_t - oy - i, x_t - ox - j), |i|, |j| <= R, inside the grid, with value
+    ky[i+R] * (kx[j+R] * deltas[t-1, sy, sx]); only positive finite values compete; frame t-1 takes the largest, the smallest
+    flat index sy w + sx on equal values: LINK 0, SCORE the value.  With no candidate it takes its row's arg-max: LINK 2,
+    SCORE 0 (as for LINK 1).  A row's pixel is clamped to the grid.  PROB, COS, SIN are read at the path pixel of frame t from
+    deltas[t] and ori[t]; ANGLE follows the evaluation kernels' rule.
+
+    return_margin: also [T,B] float64, at every LINK 0 entry the relative gap (best - second) / best of its decision, NaN
+    elsewhere.  `second` is the largest competing value whose factors (ky, kx, delta) are not all equal to the winner's —
+    candidates with the winner's own three factors give the winner's bits in any arithmetic and are settled by the index
+    rule — or 0 when there is none."""
+    deltas = np.asarray(deltas, dtype=np.float32)
+    n, b, h, w = deltas.shape[0], deltas.shape[1], deltas.shape[-2], deltas.shape[-1]
+    deltas = deltas.reshape(n, b, h, w)
+    ori = np.asarray(ori, dtype=np.float32).reshape(n, b, 2, h, w)
+    offsets = np.asarray(offsets).reshape(n, b, 2).astype(np.int64)
+    taps = np.asarray(taps, dtype=np.float32).reshape(n, b, 2, -1)
+    rows = np.asarray(rows, dtype=np.float64).reshape(n, b, 14)
+    reset = None if reset is None else np.asarray(reset).reshape(n, b)
+    r = (taps.shape[3] - 1) // 2
+    path = np.full((n, b, 8), np.nan, dtype=np.float64)
+    margin = np.full((n, b), np.nan, dtype=np.float64)
+
+    def row_pixel(t, k):
+        py, px = rows[t, k, PRED_Y], rows[t, k, PRED_X]
+        return (int(min(py, h - 1)) if py >= 0 else 0), (int(min(px, w - 1)) if px >= 0 else 0)      # +inf clamps, NaN gives 0
+
+    for k in range(b):
+        (y, x), link, score = row_pixel(n - 1, k), 1, 0.0
+        for t in range(n - 1, -1, -1):
+            c, s = ori[t, k, 0, y, x], ori[t, k, 1, y, x]
+            path[t, k] = (y, x, deltas[t, k, y, x], c, s, _angle_spec(c, s), link, score)
+            if t == 0:
+                break
+            start = (reset is not None and reset[t, k] != 0) or rows[t, k, RESET] != 0
+            best = None
+            if not start:
+                ky, kx = taps[t, k, 0].astype(np.float64), taps[t, k, 1].astype(np.float64)
+                cands = []
+                for i in range(-r, r + 1):
+                    for j in range(-r, r + 1):
+                        sy, sx = y - int(offsets[t, k, 0]) - i, x - int(offsets[t, k, 1]) - j
+                        if 0 <= sy < h and 0 <= sx < w:
+                            d = np.float64(deltas[t - 1, k, sy, sx])
+                            with np.errstate(invalid="ignore", over="ignore"):
+                                v = ky[i + r] * (kx[j + r] * d)
+                            if v > 0 and np.isfinite(v):
+                                cands.append((-v, sy * w + sx, (ky[i + r], kx[j + r], d)))
+                if cands:
+                    cands.sort(key=lambda e: (e[0], e[1]))
+                    best = cands[0]
+                    second = max([-e[0] for e in cands[1:] if e[2] != best[2]] + [0.0])
+            if best is not None:
+                (y, x), link, score = divmod(best[1], w), 0, -best[0]
+                margin[t - 1, k] = (score - second) / score
+            else:
+                (y, x), link, score = row_pixel(t - 1, k), (1 if start else 2), 0.0
+    return (path, margin) if return_margin else path
 
 
 def rigid_motion(shift_px, angle_deg, hw, centre=None):
@@ -430,6 +541,22 @@ class HistogramFilter(object):
         return rows
 
 
+def _drive_settings(hw, sigma_px, radius, outlier):
+    """The settings SequenceSmoother and MostLikelyPath share, validated: (hw, sigma_px, radius, outlier)."""
+    hw = (int(hw[0]), int(hw[1]))
+    if hw[0] <= 0 or hw[1] <= 0:
+        raise ValueError("hw must be positive")
+    sigma_px = float(sigma_px)
+    if not sigma_px >= 0:
+        raise ValueError("sigma_px must be >= 0")
+    radius = int(math.ceil(3 * sigma_px)) + 1 if radius is None else int(radius)
+    if not 0 <= radius <= MAX_RADIUS:
+        raise ValueError("radius %d outside [0, %d]: use a smaller sigma_px or pass radius" % (radius, MAX_RADIUS))
+    if not 0.0 <= float(outlier) <= 1.0:
+        raise ValueError("outlier must be in [0, 1]")
+    return hw, sigma_px, radius, float(outlier)
+
+
 class SequenceSmoother(object):
     """The forward-backward smoother of ONE track over a recorded drive: the belief of frame t given the whole drive.
 
@@ -437,22 +564,12 @@ class SequenceSmoother(object):
     posterior, then walks back with ops.belief_smooth_step / ops.belief_smooth_step_rigid: 2 launches per frame each way, no
     read-back.  Memory: h w 4 bytes per frame for the posteriors (1 MB at 512 x 512), beside the caller's heat and ori; as
     much again with keep_beliefs.  sigma_px, radius, outlier: as HistogramFilter (same ValueErrors).
-    Out of scope: several tracks per smoother, fixed-lag (online) smoothing, the most-likely-path (max-product) variant, bf16
-    maps, a change of scale between patch frames."""
+    Out of scope: several tracks per smoother, fixed-lag (online) smoothing, bf16 maps, a change of scale between patch
+    frames.  The most likely path is MostLikelyPath's."""
 
     def __init__(self, hw=(512, 512), sigma_px=1.0, radius=None, outlier=0.0, device="cuda"):
-        self.hw = (int(hw[0]), int(hw[1]))
-        if self.hw[0] <= 0 or self.hw[1] <= 0:
-            raise ValueError("hw must be positive")
-        self.sigma_px = float(sigma_px)
-        if not self.sigma_px >= 0:
-            raise ValueError("sigma_px must be >= 0")
-        self.radius = int(math.ceil(3 * self.sigma_px)) + 1 if radius is None else int(radius)
-        if not 0 <= self.radius <= MAX_RADIUS:
-            raise ValueError("radius %d outside [0, %d]: use a smaller sigma_px or pass radius" % (self.radius, MAX_RADIUS))
-        if not 0.0 <= float(outlier) <= 1.0:
-            raise ValueError("outlier must be in [0, 1]")
-        self.outlier, self.device = float(outlier), torch.device(device)
+        self.hw, self.sigma_px, self.radius, self.outlier = _drive_settings(hw, sigma_px, radius, outlier)
+        self.device = torch.device(device)
 
     def run(self, heat, ori, shift_px=None, motion=None, starts=None, keep_beliefs=False):
         """heat [T,1,h,w], ori [T,2,h,w] on the device, in drive order; exactly one of shift_px [T,2] = (dy, dx) and motion
@@ -531,6 +648,61 @@ class SequenceSmoother(object):
                  outlier=self.outlier, cut=cut[t:t + 1], beta_out=beta[t & 1], smooth=beliefs[t:t + 1] if keep_beliefs else one,
                  scratch=scratch, out=rows[t:t + 1])
         return {"filtered": filtered, "smoothed": rows, "beliefs": beliefs}
+
+
+class MostLikelyPath(object):
+    """The jointly most likely sequence of grid cells (max-product, Viterbi) of B tracks over a recorded drive.
+
+    `run` makes the forward pass with ops.belief_viterbi_step — two launches per frame for all B tracks, every map kept in a
+    [T,B,1,h,w] table — and then ONE ops.belief_backtrack launch; no read-back.  Memory: h w 4 bytes per frame and track
+    (1 MB at 512 x 512), beside the caller's heat and ori.  There are no back-pointer maps: the backtrack recomputes each link
+    at the one pixel the path visits.  sigma_px, radius, outlier: as HistogramFilter (same ValueErrors).
+    Out of scope: the rigid (KITTI) form — the warp is a bilinear mix, not a maximum, so its back-pointer needs a definition of
+    its own — stored back-pointer maps, log-domain maps, bf16 maps, fixed-lag decoding."""
+
+    def __init__(self, hw=(512, 512), sigma_px=1.0, radius=None, outlier=0.0, device="cuda"):
+        self.hw, self.sigma_px, self.radius, self.outlier = _drive_settings(hw, sigma_px, radius, outlier)
+        self.device = torch.device(device)
+
+    def run(self, heat, ori, shift_px, starts=None):
+        """heat [T,B,h,w], ori [T,B,2,h,w] (or [T,2,h,w] for B = 1) on the device, in drive order; shift_px [T,B,2] (or [T,2]
+        for B = 1) = (dy, dx), the motion INTO each frame as HistogramFilter.step takes it (a tensor on any device or an array;
+        row 0 is not used); starts [T] (all tracks) or [T,B] marks frames where a track restarts (frame 0 always does).
+        Returns {"rows": [T,B,14] of the forward pass (tracking.PRED_Y ... SURVIVED), "path": [T,B,8] (PATH_Y ... PATH_SCORE;
+        LINK: 0 chained, 1 the last frame of its segment, 2 no source pixel had mass), "deltas": the forward maps
+        [T,B,1,h,w]}, all on the device."""
+        from . import ops
+        if heat.dim() != 4 or tuple(heat.shape[2:]) != self.hw or heat.shape[0] < 1 or heat.shape[1] < 1:
+            raise ValueError("run: heat must be [T,B,%d,%d], got %s" % (self.hw + (tuple(heat.shape),)))
+        n, b = int(heat.shape[0]), int(heat.shape[1])
+        h, w = self.hw
+        if b == 1 and tuple(ori.shape) == (n, 2, h, w):
+            ori = ori.reshape(n, 1, 2, h, w)
+        if tuple(ori.shape) != (n, b, 2, h, w):
+            raise ValueError("run: ori must be [%d,%d,2,%d,%d], got %s" % (n, b, h, w, tuple(ori.shape)))
+        dev = self.device
+        shift = torch.as_tensor(shift_px).to(dev)
+        if shift.numel() != 2 * n * b:
+            raise ValueError("run: shift_px must be [%d,%d,2]" % (n, b))
+        offsets, taps = motion_taps(shift.reshape(n * b, 2), self.sigma_px, self.radius)
+        offsets, taps = offsets.reshape(n, b, 2), taps.reshape(n, b, 2, 2 * self.radius + 1)
+        reset = torch.zeros((n, b), device=dev, dtype=torch.int32)
+        if starts is not None:
+            st = np.asarray(starts)
+            if st.size not in (n, n * b):
+                raise ValueError("run: starts must be [%d] or [%d,%d]" % (n, n, b))
+            st = np.broadcast_to(st.reshape(n, -1), (n, b)).astype(np.int32)
+            reset.copy_(torch.as_tensor(np.ascontiguousarray(st)))
+        reset[0] = 1
+        table = torch.empty((n, b, 1, h, w), device=dev, dtype=torch.float32)
+        rows = torch.empty((n, b, 14), device=dev, dtype=torch.float64)
+        scratch = torch.empty((b * ops.belief_partials(h, w),), device=dev, dtype=torch.float64)
+        first = table[n - 1] if n > 1 else torch.zeros((b, 1, h, w), device=dev)                  # frame 0 resets: not read
+        for t in range(n):
+            ops.belief_viterbi_step(table[t - 1] if t else first, heat[t].reshape(b, 1, h, w), ori[t], offsets[t], taps[t],
+                                    outlier=self.outlier, reset=reset[t], post=table[t], scratch=scratch, out=rows[t])
+        path = ops.belief_backtrack(table, ori, offsets, taps, rows, reset)
+        return {"rows": rows, "path": path, "deltas": table}
 
 
 def oxford_shifts(pairs, indices=None):

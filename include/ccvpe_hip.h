@@ -552,6 +552,34 @@ int ccvpe_belief_smooth_step_rigid_f32(const float* beta, const float* heat, con
                                        void* stream);
 
 /* -------------------------------------------------------------------------------------------
+ * The most likely path over the grid (max-product / Viterbi; specification: tracking.viterbi_step_spec and
+ * tracking.backtrack_spec).  No back-pointer maps: the decision of a link is recomputed at the one pixel the path visits.
+ *
+ * ccvpe_belief_viterbi_step_f32: ccvpe_belief_step_f32 with the sums of the predict replaced by maxima,
+ *   P[y,x] = max(0, max_i ky[i+R] * max(0, max_j kx[j+R] * prior[y - oy - i, x - ox - j])),   U = P M,  post = U (float)(1 / Z)
+ * every product rounded once to fp32, NaN products ignored (fmaxf).  The map is normalised by its SUM (launch two is the
+ * filter's own), so its peak stays at or above 1 / (h w).  Arguments, checks, scratch, rows and reset rules: those of
+ * ccvpe_belief_step_f32; rows[b][13] holds sum P.  Two launches, no atomics.
+ *
+ * ccvpe_belief_backtrack_f32: ONE launch for a whole drive, one workgroup per track.  deltas [T,B,h*w]: the posts of the
+ * forward pass; ori [T,B,2,h*w]; offsets [T,B,2] and taps [T,B,2,2R+1]: the motion INTO each frame; rows [T,B,14]: the forward
+ * rows; reset [T,B] or NULL (frame 0 always starts a segment); path [T,B,8] doubles out:
+ *   { y, x, deltas there, cos, sin, angle, link, score }
+ * Frame T-1 takes its row's arg-max (link 1).  For t >= 1: if reset[t] != 0 or rows[t][7] != 0, frame t-1 takes its row's
+ * arg-max (link 1); else the candidates are the source pixels (y_t - oy - i, x_t - ox - j), |i|, |j| <= R, inside the grid,
+ * with value ky[i+R] * (kx[j+R] * deltas[t-1]) (fp32, each product rounded once — the bits of P there); only positive finite
+ * values compete; the largest wins, the smaller flat index on equal values (link 0, score = the value); with no candidate
+ * frame t-1 takes its row's arg-max (link 2, score 0).  Pixels read from rows are clamped to the grid.  path must not
+ * overlap an input; rows and path 8-byte aligned; 0 <= radius <= 32.
+ * ----------------------------------------------------------------------------------------- */
+int ccvpe_belief_viterbi_step_f32(const float* prior, const float* heat, const float* ori, const int* offsets, const float* taps,
+                                  int radius, float outlier, const int* reset, float* post, double* scratch, double* rows,
+                                  int batch, int h, int w, void* stream);
+int ccvpe_belief_backtrack_f32(const float* deltas, const float* ori, const int* offsets, const float* taps, int radius,
+                               const double* rows, const int* reset /* may be null */, double* path, int frames, int batch, int h,
+                               int w, void* stream);
+
+/* -------------------------------------------------------------------------------------------
  * Losses (losses.py:4-29), device scalars out.  `acc` is caller-provided scratch.
  *   infoNCE: accumulates num = sum_{label>1e-2} log(softmax(s/T))*label and den = sum label over
  *            the whole batch; loss = -num/den.            scores/labels [B,n]
