@@ -2,32 +2,34 @@
 // per track in two launches — predict (integer shift + separable blur of the prior) x measure (the network's heat-map mixed
 // with a uniform outlier floor), then renormalise and read the estimate off the posterior.
 //
-// Launch one, belief_predict_kernel: a workgroup owns a (track, 16 x 64 output tile) pair.  The prior tile plus its R halo is
-// staged in LDS already shifted by the track's integer offset, zero outside the grid; the row pass (16 B LDS reads, four
-// outputs per lane) and the column pass (a four-deep register window down the column) run in fp32; the product with
-// M = (1 - a) heat + a / (h w) is written as U and the tile's sums (double), arg-max candidate and moment sums go to one
-// record per workgroup — for U and for M, so that a reset needs no third pass over the maps.
-// Launch two, belief_finish_kernel: every workgroup of a track merges the track's records in the same fixed order, decides
-// the reset, scales its slice of the map by (float)(1 / Z), and the first slice writes the row.
+// Launch one, belief_step_kernel<MODE, WARP, VEC>: a workgroup owns a (track, 16 x 64 output tile) pair.  The tile plus its R
+// halo is staged in LDS already moved, zero outside the grid; the row pass (16 B LDS reads, four outputs per lane) and the
+// column pass (a four-deep register window down the column) run in fp32; the product with the second factor is written and
+// the tile's sums (double), arg-max candidate and moment sums go to one record per workgroup — for the product and for the
+// factor, so that a reset needs no third pass over the maps.  The one kernel has three axes:
+//   MODE  BF_SUM   the filter (ccvpe_belief_step_f32 / _rigid_f32): U = blur(moved prior) M, M = (1 - a) heat + a / (h w).
+//         BF_MAX   the max-product step (ccvpe_belief_viterbi_step_f32; tracking.viterbi_step_spec): bf_passes in its max form
+//                  (sums over taps become maxima), everything else BF_SUM's.
+//         BF_BACK  the backward step of the forward-backward smoother (ccvpe_belief_smooth_step_f32 / _rigid_f32;
+//                  tracking.smooth_step_spec / smooth_step_rigid_spec): the staging forms G = fma(1 - a, heat, floor) beta on the
+//                  way into LDS — the measurement enters BEFORE the blur — with the offsets added instead of subtracted (the
+//                  rigid form walks the inverted motion); bf_passes indexes the taps in reverse, which together with the sign
+//                  is the adjoint of the predict; bf_epilogue multiplies with the stored posterior alpha, writes B' and
+//                  V = alpha B' and the forward record with alpha in M's place.
+//   WARP  false    bf_stage_shift: the map moved by the track's whole-pixel offset.
+//         true     bf_stage_warp (tracking.step_rigid_spec): the map resampled bilinearly through the track's inverse motion
+//                  map; only the staging differs.  BF_SUM and BF_BACK only, and VEC does not apply.
+//   VEC   16-byte loads of the staged maps (w % 4 == 0 and 16-byte aligned maps); the values in LDS are the scalar form's.
+// Launch two, belief_finish_kernel<VEC, BACK>: every workgroup of a track merges the track's records in the same fixed order
+// (bf_merge_records), decides the state, scales its slice of the map by (float)(1 / Z) — BACK: both maps, or the fallback
+// written — and the first slice writes the row (bf_write_row).
 // No floating-point atomics: two runs are bit-identical.
-// The rigid step (ccvpe_belief_step_rigid_f32; tracking.step_rigid_spec) replaces only the staging of launch one:
-// belief_predict_rigid_kernel fills the LDS tile with the prior resampled bilinearly through the track's inverse motion map and
-// then runs the same passes (bf_blur_measure); launch two is the same kernel.
+// What the modes do not share: the value a staged pixel takes (bf_src), the second output map, the state rule and the
+// per-element update of launch two.
 //
-// The backward step of the forward-backward smoother (ccvpe_belief_smooth_step_f32 / _rigid_f32; tracking.smooth_step_spec /
-// smooth_step_rigid_spec) has the same two-launch shape and is built from the same pieces.  Launch one, belief_smooth_kernel /
-// belief_smooth_rigid_kernel: the staging helpers (bf_stage_shift, bf_stage_warp) form G = fma(1 - a, heat, floor) beta on the
-// way into LDS — the measurement enters BEFORE the blur — with the offsets added instead of subtracted (the rigid form walks
-// the inverted motion); bf_passes runs the row and column passes with the taps indexed in reverse, which together with the
-// sign is the adjoint of the predict; bf_epilogue multiplies with the stored posterior alpha, writes B' and V = alpha B' and
-// the forward record with alpha in M's place.  Launch two, belief_smooth_finish_kernel: the shared record merge
-// (bf_merge_records), the state, BOTH maps scaled (or the fallback written), the shared row (bf_write_row).
-// What is not shared: the value a staged pixel takes (bf_src), the second output map and the two-map scaling loop.
-//
-// The most likely path (ccvpe_belief_viterbi_step_f32, ccvpe_belief_backtrack_f32; tracking.viterbi_step_spec / backtrack_spec):
-// belief_viterbi_kernel is the predict kernel with bf_passes in its max form (sums over taps become maxima) and launch two is
-// belief_finish_kernel; belief_backtrack_kernel walks a whole drive in one launch, a workgroup per track, and recomputes each
-// link's decision at the one pixel the path visits — there are no back-pointer maps.
+// The most likely path (ccvpe_belief_backtrack_f32; tracking.backtrack_spec): belief_backtrack_kernel walks a whole drive of
+// BF_MAX maps in one launch, a workgroup per track, and recomputes each link's decision at the one pixel the path visits —
+// there are no back-pointer maps.
 #include "common.h"
 
 namespace ccvpe {
@@ -79,11 +81,18 @@ __device__ __forceinline__ void bf_moments(double* m, float v, int y, int x) {
   m[5] = fma(d * dy, dx, m[5]);
 }
 
+enum BfMode { BF_SUM, BF_MAX, BF_BACK };
+
+// The measurement M = (1 - a) heat + a / (h w), one fused multiply-add wherever it is formed
+__device__ __forceinline__ float bf_measure(float heat, float one_minus_a, float floor_m) {
+  return fmaf(one_minus_a, heat, floor_m);
+}
+
 // The value a staged pixel takes from global memory: the prior itself (the forward step), or the backward step's
-// G = M beta with M = fma(1 - a, heat, floor) formed on the way into LDS (v = heat, v2 = beta).
+// G = M beta formed on the way into LDS (v = heat, v2 = beta).
 template <bool SMOOTH>
 __device__ __forceinline__ float bf_src(float v, float v2, float one_minus_a, float floor_m) {
-  return SMOOTH ? __fmul_rn(fmaf(one_minus_a, v, floor_m), v2) : v;
+  return SMOOTH ? __fmul_rn(bf_measure(v, one_minus_a, floor_m), v2) : v;
 }
 
 // Stage the tile plus its R halo of a map moved by whole pixels: T[r][c] = src(gy0 + r, gx0 + c), zero outside the grid.
@@ -136,7 +145,10 @@ __device__ __forceinline__ void bf_stage_shift(float* T, const float* __restrict
 // The barrier after the staging of T, the row pass and the column pass: q[o] is the blurred value of tile pixel
 // (4 (tid / 64) + o, tid % 64).  REV indexes both tap vectors in reverse (the backward step's adjoint blur).  MAXP is the
 // max-product form (tracking.viterbi_step_spec): every sum over taps becomes a maximum, acc = fmaxf(acc, k * w) from a zero
-// start — a NaN product is ignored and negative values count as zero; staging, layout and barriers are the same.
+// start — a NaN product is ignored and negative values count as zero; staging, layout and barriers are the same:
+// P[y,x] = max_i ky[i+R] max_j kx[j+R] delta[y - oy - i, x - ox - j].  Every product is rounded once and a maximum rounds
+// nothing, so P carries the bits of __fmul_rn(ky, __fmul_rn(kx, delta)) at its winning source pixel — what
+// belief_backtrack_kernel recomputes.
 template <bool REV, bool MAXP = false>
 __device__ __forceinline__ void bf_passes(const float* T, float* mid, const float* __restrict__ taps, int R, bool skip, int b,
                                           float* q) {
@@ -215,7 +227,7 @@ __device__ __forceinline__ void bf_epilogue(const float* q, const float* __restr
       if (y < h) {
         const size_t e = (size_t)y * w + x;
         const float av = aux[(size_t)b * n + e];
-        const float mv = SMOOTH ? av : fmaf(one_minus_a, av, floor_m);
+        const float mv = SMOOTH ? av : bf_measure(av, one_minus_a, floor_m);
         const float uv = q[o] * mv;
         if (!skip) {
           post[(size_t)b * n + e] = uv;
@@ -257,67 +269,6 @@ __device__ __forceinline__ void bf_epilogue(const float* q, const float* __restr
     rec[15] = (double)am.v; rec[16] = (double)am.i;
     rec[17] = 0.0;
   }
-}
-
-// Everything after the staging of T (the moved prior of the tile with its R halo), for both predict kernels: the barrier, the
-// row pass, the column pass, the measure, U and the tile's record.
-__device__ __forceinline__ void bf_blur_measure(const float* T, float* mid, const float* __restrict__ heat,
-                                                const float* __restrict__ taps, int R, float one_minus_a, float floor_m,
-                                                bool skip, float* __restrict__ post, double* __restrict__ scratch, int b,
-                                                int tile, int ntiles, int y0, int x0, int h, int w) {
-  float q[4];
-  bf_passes<false>(T, mid, taps, R, skip, b, q);
-  bf_epilogue<false>(q, heat, one_minus_a, floor_m, skip, post, nullptr, scratch, b, tile, ntiles, y0, x0, h, w);
-}
-
-template <bool VEC>
-__global__ __launch_bounds__(256) void belief_predict_kernel(const float* __restrict__ prior, const float* __restrict__ heat,
-                                                             const int* __restrict__ offsets, const float* __restrict__ taps,
-                                                             int R, float one_minus_a, float floor_m,
-                                                             const int* __restrict__ reset, float* __restrict__ post,
-                                                             double* __restrict__ scratch, int h, int w, int ntx, int nty) {
-  extern __shared__ cc_f32x4 bf_smem[];
-  const int ntiles = ntx * nty;
-  const int b = blockIdx.x / ntiles, tile = blockIdx.x - b * ntiles;
-  const int y0 = (tile / ntx) * BF_TH, x0 = (tile % ntx) * BF_TW;
-  const int rows = BF_TH + 2 * R, PW = bf_pitch(R);
-  float* T = reinterpret_cast<float*>(bf_smem);                  // [rows][PW]: T[r][c] = prior(y0 + r - R - oy, x0 + c - R - ox)
-  float* mid = T + rows * PW;                                    // [rows][BF_TW]: the row pass
-  const bool skip = reset != nullptr && reset[b] != 0;           // a reset track starts from the measurement: no predict
-  if (!skip) {
-    const long long oy = offsets[2 * b], ox = offsets[2 * b + 1];
-    bf_stage_shift<VEC, false>(T, prior + (size_t)b * h * w, nullptr, one_minus_a, floor_m, (long long)y0 - R - oy,
-                               (long long)x0 - R - ox, rows, PW, h, w);
-  }
-  bf_blur_measure(T, mid, heat, taps, R, one_minus_a, floor_m, skip, post, scratch, b, tile, ntiles, y0, x0, h, w);
-}
-
-// Launch one of the max-product step (tracking.viterbi_step_spec): the predict kernel with the passes in their max form,
-// P[y,x] = max_i ky[i+R] max_j kx[j+R] delta[y - oy - i, x - ox - j].  Every product is rounded once and a maximum rounds
-// nothing, so P carries the bits of __fmul_rn(ky, __fmul_rn(kx, delta)) at its winning source pixel — what
-// belief_backtrack_kernel recomputes.  Launch two is belief_finish_kernel: the map is normalised by its sum.
-template <bool VEC>
-__global__ __launch_bounds__(256) void belief_viterbi_kernel(const float* __restrict__ prior, const float* __restrict__ heat,
-                                                             const int* __restrict__ offsets, const float* __restrict__ taps,
-                                                             int R, float one_minus_a, float floor_m,
-                                                             const int* __restrict__ reset, float* __restrict__ post,
-                                                             double* __restrict__ scratch, int h, int w, int ntx, int nty) {
-  extern __shared__ cc_f32x4 bf_smem[];
-  const int ntiles = ntx * nty;
-  const int b = blockIdx.x / ntiles, tile = blockIdx.x - b * ntiles;
-  const int y0 = (tile / ntx) * BF_TH, x0 = (tile % ntx) * BF_TW;
-  const int rows = BF_TH + 2 * R, PW = bf_pitch(R);
-  float* T = reinterpret_cast<float*>(bf_smem);
-  float* mid = T + rows * PW;
-  const bool skip = reset != nullptr && reset[b] != 0;
-  if (!skip) {
-    const long long oy = offsets[2 * b], ox = offsets[2 * b + 1];
-    bf_stage_shift<VEC, false>(T, prior + (size_t)b * h * w, nullptr, one_minus_a, floor_m, (long long)y0 - R - oy,
-                               (long long)x0 - R - ox, rows, PW, h, w);
-  }
-  float q[4];
-  bf_passes<false, true>(T, mid, taps, R, skip, b, q);
-  bf_epilogue<false>(q, heat, one_minus_a, floor_m, skip, post, nullptr, scratch, b, tile, ntiles, y0, x0, h, w);
 }
 
 // The most likely path of every track over a whole drive (tracking.backtrack_spec), one launch: a workgroup owns a track and
@@ -404,35 +355,6 @@ __global__ __launch_bounds__(256) void belief_backtrack_kernel(const float* __re
   }
 }
 
-// Launch one of the backward step (tracking.smooth_step_spec): the forward step's own offsets and taps, used the other way
-// round — T[r][c] = G(y0 + r - R + oy, x0 + c - R + ox) and the taps in reverse, B'[y,x] = sum_ij ky[i+R] kx[j+R]
-// G[y + oy + i, x + ox + j].  The sign lives in the 64-bit index arithmetic: no offset is negated.
-template <bool VEC>
-__global__ __launch_bounds__(256) void belief_smooth_kernel(const float* __restrict__ beta, const float* __restrict__ heat,
-                                                            const float* __restrict__ alpha, const int* __restrict__ offsets,
-                                                            const float* __restrict__ taps, int R, float one_minus_a,
-                                                            float floor_m, const int* __restrict__ cut,
-                                                            float* __restrict__ beta_out, float* __restrict__ smooth,
-                                                            double* __restrict__ scratch, int h, int w, int ntx, int nty) {
-  extern __shared__ cc_f32x4 bf_smem[];
-  const int ntiles = ntx * nty;
-  const int b = blockIdx.x / ntiles, tile = blockIdx.x - b * ntiles;
-  const int y0 = (tile / ntx) * BF_TH, x0 = (tile % ntx) * BF_TW;
-  const int rows = BF_TH + 2 * R, PW = bf_pitch(R);
-  float* T = reinterpret_cast<float*>(bf_smem);
-  float* mid = T + rows * PW;
-  const bool skip = cut != nullptr && cut[b] != 0;               // the last frame of its segment: no message to bring back
-  if (!skip) {
-    const long long oy = offsets[2 * b], ox = offsets[2 * b + 1];
-    const size_t n = (size_t)h * w;
-    bf_stage_shift<VEC, true>(T, heat + (size_t)b * n, beta + (size_t)b * n, one_minus_a, floor_m, (long long)y0 - R + oy,
-                              (long long)x0 - R + ox, rows, PW, h, w);
-  }
-  float q[4];
-  bf_passes<true>(T, mid, taps, R, skip, b, q);
-  bf_epilogue<true>(q, alpha, one_minus_a, floor_m, skip, smooth, beta_out, scratch, b, tile, ntiles, y0, x0, h, w);
-}
-
 // (a0 y + a1 x) + a2 with every product and every sum rounded on its own, as numpy evaluates the specification's expression.
 // The operators are written out under contract(off): __dmul_rn / __dadd_rn are plain inline `*` and `+` in this toolchain, and
 // the compiler fuses them into a multiply-add across the call (seen in the ISA) — the pragma only governs what it encloses.
@@ -503,56 +425,62 @@ __device__ __forceinline__ void bf_stage_warp(float* T, const float* __restrict_
   }
 }
 
-// Launch one of the rigid step (tracking.step_rigid_spec): T holds W, the prior resampled through the track's inverse map.
-__global__ __launch_bounds__(256) void belief_predict_rigid_kernel(const float* __restrict__ prior, const float* __restrict__ heat,
-                                                                   const double* __restrict__ motion, const float* __restrict__ taps,
-                                                                   int R, float one_minus_a, float floor_m,
-                                                                   const int* __restrict__ reset, float* __restrict__ post,
-                                                                   double* __restrict__ scratch, int h, int w, int ntx, int nty) {
-  extern __shared__ cc_f32x4 bf_smem[];
-  const int ntiles = ntx * nty;
-  const int b = blockIdx.x / ntiles, tile = blockIdx.x - b * ntiles;
-  const int y0 = (tile / ntx) * BF_TH, x0 = (tile % ntx) * BF_TW;
-  const int rows = BF_TH + 2 * R, PW = bf_pitch(R);
-  float* T = reinterpret_cast<float*>(bf_smem);                  // [rows][PW]: T[r][c] = W(y0 + r - R, x0 + c - R), c < cols
-  float* mid = T + rows * PW;
-  const bool skip = reset != nullptr && reset[b] != 0;
-  if (!skip) {
-    const double* m = motion + (size_t)b * 6;
-    const double mm[6] = {m[0], m[1], m[2], m[3], m[4], m[5]};
-    bf_stage_warp<false>(T, prior + (size_t)b * h * w, nullptr, mm, one_minus_a, floor_m, R, y0, x0, h, w);
-  }
-  bf_blur_measure(T, mid, heat, taps, R, one_minus_a, floor_m, skip, post, scratch, b, tile, ntiles, y0, x0, h, w);
-}
+// The arguments of launch one, by value.  prev: the prior (forward) or beta, the message of frame t (BF_BACK); alpha: the
+// stored posterior (BF_BACK only); move: offsets int32 [B,2] or, WARP, motion double [B,6]; skip: reset (forward) or cut
+// (BF_BACK) flags, or null; out: post / smooth; beta_out: BF_BACK only.
+struct BfStep {
+  const float *prev, *heat, *alpha;
+  const void* move;
+  const float* taps;
+  const int* skip;
+  float *out, *beta_out;
+  double* scratch;
+  int R, h, w, ntx, nty;
+  float one_minus_a, floor_m;
+};
 
-// Launch one of the rigid backward step (tracking.smooth_step_rigid_spec): T holds G = M beta of frame t resampled along the
-// REVERSE motion — the forward step's motion row, inverted here — then the reversed-tap blur and the shared epilogue.  A
-// bilinear gather's adjoint would be a scatter: this is the same continuous model discretised the other way, not the exact
-// adjoint of the rigid predict (for whole-pixel shifts and quarter turns the two coincide).
-__global__ __launch_bounds__(256) void belief_smooth_rigid_kernel(const float* __restrict__ beta, const float* __restrict__ heat,
-                                                                  const float* __restrict__ alpha,
-                                                                  const double* __restrict__ motion,
-                                                                  const float* __restrict__ taps, int R, float one_minus_a,
-                                                                  float floor_m, const int* __restrict__ cut,
-                                                                  float* __restrict__ beta_out, float* __restrict__ smooth,
-                                                                  double* __restrict__ scratch, int h, int w, int ntx, int nty) {
+// Launch one of every step.  Forward, shift: T[r][c] = prior(y0 + r - R - oy, x0 + c - R - ox).  BF_BACK, shift
+// (tracking.smooth_step_spec): the forward step's own offsets and taps, used the other way round —
+// T[r][c] = G(y0 + r - R + oy, x0 + c - R + ox) and the taps in reverse, B'[y,x] = sum_ij ky[i+R] kx[j+R]
+// G[y + oy + i, x + ox + j].  The sign lives in the 64-bit index arithmetic: no offset is negated.  WARP: T[r][c] =
+// W(y0 + r - R, x0 + c - R), c < 64 + 2R, the map resampled through the track's inverse map; BF_BACK
+// (tracking.smooth_step_rigid_spec) resamples G = M beta of frame t along the REVERSE motion — the forward step's motion row,
+// inverted here.  A bilinear gather's adjoint would be a scatter: this is the same continuous model discretised the other
+// way, not the exact adjoint of the rigid predict (for whole-pixel shifts and quarter turns the two coincide).
+template <int MODE, bool WARP, bool VEC>
+__global__ __launch_bounds__(256) void belief_step_kernel(const BfStep a) {
   extern __shared__ cc_f32x4 bf_smem[];
-  const int ntiles = ntx * nty;
+  constexpr bool BACK = MODE == BF_BACK;
+  const int R = a.R, h = a.h, w = a.w;
+  const int ntiles = a.ntx * a.nty;
   const int b = blockIdx.x / ntiles, tile = blockIdx.x - b * ntiles;
-  const int y0 = (tile / ntx) * BF_TH, x0 = (tile % ntx) * BF_TW;
+  const int y0 = (tile / a.ntx) * BF_TH, x0 = (tile % a.ntx) * BF_TW;
   const int rows = BF_TH + 2 * R, PW = bf_pitch(R);
-  float* T = reinterpret_cast<float*>(bf_smem);
-  float* mid = T + rows * PW;
-  const bool skip = cut != nullptr && cut[b] != 0;
+  float* T = reinterpret_cast<float*>(bf_smem);                  // [rows][PW]: the moved map
+  float* mid = T + rows * PW;                                    // [rows][BF_TW]: the row pass
+  // a reset track starts from the measurement: no predict; a cut frame is the last of its segment: no message to bring back
+  const bool skip = a.skip != nullptr && a.skip[b] != 0;
   if (!skip) {
-    double back[6];
-    bf_invert_motion(motion + (size_t)b * 6, back);
     const size_t n = (size_t)h * w;
-    bf_stage_warp<true>(T, heat + (size_t)b * n, beta + (size_t)b * n, back, one_minus_a, floor_m, R, y0, x0, h, w);
+    const float* src = (BACK ? a.heat : a.prev) + (size_t)b * n;
+    const float* src2 = BACK ? a.prev + (size_t)b * n : nullptr;
+    if (WARP) {
+      const double* m = static_cast<const double*>(a.move) + (size_t)b * 6;
+      double mm[6] = {m[0], m[1], m[2], m[3], m[4], m[5]};
+      if (BACK) bf_invert_motion(m, mm);
+      bf_stage_warp<BACK>(T, src, src2, mm, a.one_minus_a, a.floor_m, R, y0, x0, h, w);
+    } else {
+      const int* offsets = static_cast<const int*>(a.move);
+      const long long oy = offsets[2 * b], ox = offsets[2 * b + 1];
+      const long long gy0 = (long long)y0 - R, gx0 = (long long)x0 - R;
+      bf_stage_shift<VEC, BACK>(T, src, src2, a.one_minus_a, a.floor_m, BACK ? gy0 + oy : gy0 - oy, BACK ? gx0 + ox : gx0 - ox,
+                                rows, PW, h, w);
+    }
   }
   float q[4];
-  bf_passes<true>(T, mid, taps, R, skip, b, q);
-  bf_epilogue<true>(q, alpha, one_minus_a, floor_m, skip, smooth, beta_out, scratch, b, tile, ntiles, y0, x0, h, w);
+  bf_passes<BACK, MODE == BF_MAX>(T, mid, a.taps, R, skip, b, q);
+  bf_epilogue<BACK>(q, BACK ? a.alpha : a.heat, a.one_minus_a, a.floor_m, skip, a.out, a.beta_out, a.scratch, b, tile, ntiles,
+                    y0, x0, h, w);
 }
 
 // The track's records, merged in a fixed order by every workgroup of launch two: lane-strided, butterfly, waves 0..3.  fin
@@ -620,101 +548,78 @@ __device__ __forceinline__ void bf_write_row(double* __restrict__ r, const float
   r[13] = S;
 }
 
-template <bool VEC>
-__global__ __launch_bounds__(256) void belief_finish_kernel(const float* __restrict__ heat, const float* __restrict__ ori,
-                                                            float one_minus_a, float floor_m, const int* __restrict__ reset,
-                                                            float* __restrict__ post, const double* __restrict__ scratch,
-                                                            double* __restrict__ rows, int h, int w, int ntiles, int slices,
-                                                            int slice_len) {
+// Launch two.  Forward (aux = heat, out = post): state 1 for a reset track, 2 when not (Z > 0 and finite); state 0 scales U by
+// (float)(1 / Z), otherwise post = M (float)(1 / sum M).  BACK (aux = alpha, out = smooth): state 1 for a cut track, 2 when not
+// (Z > 0 and finite and S > 0 and finite); state 0 scales V by (float)(1 / Z) and B' by (float)(1 / S); otherwise smooth =
+// alpha (float)(1 / sum alpha) and the message is uniform.
+template <bool VEC, bool BACK>
+__global__ __launch_bounds__(256) void belief_finish_kernel(const float* __restrict__ aux, const float* __restrict__ ori,
+                                                            float one_minus_a, float floor_m, const int* __restrict__ skip,
+                                                            float* __restrict__ out, float* __restrict__ beta_out,
+                                                            const double* __restrict__ scratch, double* __restrict__ rows, int h,
+                                                            int w, int ntiles, int slices, int slice_len) {
   __shared__ double fin[BF_NSUM];
   __shared__ float fv[2];
   __shared__ int fi[2];
   const int tid = threadIdx.x;
   const int b = blockIdx.x / slices, sl = blockIdx.x - b * slices;
   bf_merge_records(scratch + (size_t)b * ntiles * BF_REC, ntiles, fin, fv, fi);
-  int rst = (reset != nullptr && reset[b] != 0) ? 1 : 0;
-  double Z = fin[1];
-  if (!rst && !(Z > 0.0 && Z < (double)INFINITY)) rst = 2;
-  const int sel = rst ? 1 : 0;                                   // the M record serves a reset
-  const double* mom = fin + 1 + 6 * sel;
-  Z = mom[0];
-  const float inv = (float)(1.0 / Z);
-  const size_t n = (size_t)h * w;
-  const float* hb = heat + (size_t)b * n;
-  float* pb = post + (size_t)b * n;
-  const size_t e0 = (size_t)sl * slice_len, e1 = e0 + slice_len < n ? e0 + slice_len : n;
-  if (VEC) {                                                     // n % 4 == 0, slice_len % 4 == 0, 16-byte aligned maps
-    for (size_t i = e0 + 4 * (size_t)tid; i < e1; i += 1024) {
-      cc_f32x4 v;
-      if (rst) {
-        const cc_f32x4 hv = *reinterpret_cast<const cc_f32x4*>(hb + i);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) v[k] = fmaf(one_minus_a, hv[k], floor_m) * inv;
-      } else {
-        v = *reinterpret_cast<const cc_f32x4*>(pb + i);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) v[k] *= inv;
-      }
-      *reinterpret_cast<cc_f32x4*>(pb + i) = v;
-    }
-  } else {
-    for (size_t i = e0 + tid; i < e1; i += 256) pb[i] = (rst ? fmaf(one_minus_a, hb[i], floor_m) : pb[i]) * inv;
-  }
-  if (sl != 0 || tid != 0) return;
-  bf_write_row(rows + (size_t)b * 14, ori, b, n, w, fi[sel], fv[sel], inv, mom, Z, rst, fin[0]);
-}
-
-// Launch two of the backward step: state 1 for a cut track, 2 when not (Z > 0 and finite and S > 0 and finite); state 0 scales
-// V by (float)(1 / Z) and B' by (float)(1 / S); otherwise smooth = alpha (float)(1 / sum alpha) and the message is uniform.
-template <bool VEC>
-__global__ __launch_bounds__(256) void belief_smooth_finish_kernel(const float* __restrict__ alpha, const float* __restrict__ ori,
-                                                                   const int* __restrict__ cut, float* __restrict__ beta_out,
-                                                                   float* __restrict__ smooth,
-                                                                   const double* __restrict__ scratch,
-                                                                   double* __restrict__ rows, int h, int w, int ntiles,
-                                                                   int slices, int slice_len) {
-  __shared__ double fin[BF_NSUM];
-  __shared__ float fv[2];
-  __shared__ int fi[2];
-  const int tid = threadIdx.x;
-  const int b = blockIdx.x / slices, sl = blockIdx.x - b * slices;
-  bf_merge_records(scratch + (size_t)b * ntiles * BF_REC, ntiles, fin, fv, fi);
-  int state = (cut != nullptr && cut[b] != 0) ? 1 : 0;
+  int state = (skip != nullptr && skip[b] != 0) ? 1 : 0;
   const double S = fin[0];
   double Z = fin[1];
-  if (!state && !(Z > 0.0 && Z < (double)INFINITY && S > 0.0 && S < (double)INFINITY)) state = 2;
-  const int sel = state ? 1 : 0;                                 // the alpha record serves the fallback
+  if (!state && !(Z > 0.0 && Z < (double)INFINITY && (!BACK || (S > 0.0 && S < (double)INFINITY)))) state = 2;
+  const int sel = state ? 1 : 0;                                 // the M / alpha record serves a reset / the fallback
   const double* mom = fin + 1 + 6 * sel;
   Z = mom[0];
   const size_t n = (size_t)h * w;
   const float inv = (float)(1.0 / Z);
-  const float invs = state ? (float)(1.0 / (double)n) : (float)(1.0 / S);
-  const float* ab = alpha + (size_t)b * n;
-  float* sb = smooth + (size_t)b * n;
-  float* bb = beta_out + (size_t)b * n;
+  const float* ab = aux + (size_t)b * n;
+  float* ob = out + (size_t)b * n;
   const size_t e0 = (size_t)sl * slice_len, e1 = e0 + slice_len < n ? e0 + slice_len : n;
-  if (VEC) {                                                     // n % 4 == 0, slice_len % 4 == 0, 16-byte aligned maps
+  // The per-element update, one loop per mode: VEC means n % 4 == 0, slice_len % 4 == 0 and 16-byte aligned maps.  The
+  // backward form issues both loads before either product (one merged loop serialised them: 5 % at B = 1).
+  if constexpr (BACK) {
+    const float invs = state ? (float)(1.0 / (double)n) : (float)(1.0 / S);
+    float* bb = beta_out + (size_t)b * n;
+    if (VEC) {
+      for (size_t i = e0 + 4 * (size_t)tid; i < e1; i += 1024) {
+        cc_f32x4 v, m;
+        if (state) {
+          v = *reinterpret_cast<const cc_f32x4*>(ab + i);
+          m = (cc_f32x4){invs, invs, invs, invs};
+#pragma unroll
+          for (int k = 0; k < 4; ++k) v[k] *= inv;
+        } else {
+          v = *reinterpret_cast<const cc_f32x4*>(ob + i);
+          m = *reinterpret_cast<const cc_f32x4*>(bb + i);
+#pragma unroll
+          for (int k = 0; k < 4; ++k) { v[k] *= inv; m[k] *= invs; }
+        }
+        *reinterpret_cast<cc_f32x4*>(ob + i) = v;
+        *reinterpret_cast<cc_f32x4*>(bb + i) = m;
+      }
+    } else {
+      for (size_t i = e0 + tid; i < e1; i += 256) {
+        ob[i] = (state ? ab[i] : ob[i]) * inv;
+        bb[i] = state ? invs : bb[i] * invs;
+      }
+    }
+  } else if (VEC) {
     for (size_t i = e0 + 4 * (size_t)tid; i < e1; i += 1024) {
-      cc_f32x4 v, m;
+      cc_f32x4 v;
       if (state) {
-        v = *reinterpret_cast<const cc_f32x4*>(ab + i);
-        m = (cc_f32x4){invs, invs, invs, invs};
+        const cc_f32x4 hv = *reinterpret_cast<const cc_f32x4*>(ab + i);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] = bf_measure(hv[k], one_minus_a, floor_m) * inv;
+      } else {
+        v = *reinterpret_cast<const cc_f32x4*>(ob + i);
 #pragma unroll
         for (int k = 0; k < 4; ++k) v[k] *= inv;
-      } else {
-        v = *reinterpret_cast<const cc_f32x4*>(sb + i);
-        m = *reinterpret_cast<const cc_f32x4*>(bb + i);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) { v[k] *= inv; m[k] *= invs; }
       }
-      *reinterpret_cast<cc_f32x4*>(sb + i) = v;
-      *reinterpret_cast<cc_f32x4*>(bb + i) = m;
+      *reinterpret_cast<cc_f32x4*>(ob + i) = v;
     }
   } else {
-    for (size_t i = e0 + tid; i < e1; i += 256) {
-      sb[i] = (state ? ab[i] : sb[i]) * inv;
-      bb[i] = state ? invs : bb[i] * invs;
-    }
+    for (size_t i = e0 + tid; i < e1; i += 256) ob[i] = (state ? bf_measure(ab[i], one_minus_a, floor_m) : ob[i]) * inv;
   }
   if (sl != 0 || tid != 0) return;
   bf_write_row(rows + (size_t)b * 14, ori, b, n, w, fi[sel], fv[sel], inv, mom, Z, state, S);
@@ -799,36 +704,43 @@ static int bf_slices(const char* who, int batch, size_t n, int* slices, int* sli
   return CCVPE_OK;
 }
 
-static int bf_finish(const float* heat, const float* ori, float one_minus_a, float floor_m, const int* reset, float* post,
-                     double* scratch, double* rows, int batch, int h, int w, long long ntiles, hipStream_t st) {
-  const size_t n = (size_t)h * w;
-  int slices, slice_len;
-  if (int rc = bf_slices("belief_step", batch, n, &slices, &slice_len)) return rc;
-  const bool vec2 = (n % 4) == 0 && aligned16(heat) && aligned16(post);
-  const dim3 grid2((unsigned)(slices * batch));
-  if (vec2)
-    hipLaunchKernelGGL(belief_finish_kernel<true>, grid2, dim3(256), 0, st, heat, ori, one_minus_a, floor_m, reset, post, scratch,
-                       rows, h, w, (int)ntiles, slices, slice_len);
-  else
-    hipLaunchKernelGGL(belief_finish_kernel<false>, grid2, dim3(256), 0, st, heat, ori, one_minus_a, floor_m, reset, post, scratch,
-                       rows, h, w, (int)ntiles, slices, slice_len);
-  return check_launch("belief_finish_kernel");
+template <int MODE, bool WARP, bool VEC>
+static int bf_launch_one(const char* who, const BfStep& a, unsigned grid, int smem, hipStream_t st) {
+  auto kern = belief_step_kernel<MODE, WARP, VEC>;
+  static DevCache lds_set;                                       // per instantiation, so per kernel
+  if (int rc = ensure_dyn_lds(lds_set, kern, smem, who)) return rc;
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), smem, st, a);
+  return check_launch("belief_step_kernel");
 }
 
-static int bf_smooth_finish(const float* alpha, const float* ori, const int* cut, float* beta_out, float* smooth, double* scratch,
-                            double* rows, int batch, int h, int w, long long ntiles, hipStream_t st) {
-  const size_t n = (size_t)h * w;
+// Both launches of a step whose arguments have passed bf_check (which gave a.ntx, a.nty).  `a` comes with everything but the
+// two scalars of the measurement; `who` names the entry should the dynamic-LDS opt-in fail.
+template <int MODE, bool WARP>
+static int bf_run(const char* who, BfStep a, const float* ori, float outlier, double* rows, int batch, void* stream) {
+  constexpr bool BACK = MODE == BF_BACK;
+  hipStream_t st = (hipStream_t)stream;
+  const long long ntiles = (long long)a.ntx * a.nty;
+  const size_t n = (size_t)a.h * a.w;
+  a.one_minus_a = 1.0f - outlier;
+  a.floor_m = outlier / (float)n;
+  const int smem = (int)sizeof(float) * (BF_TH + 2 * a.R) * (bf_pitch(a.R) + BF_TW);      // 64 000 B at R = 32
+  const unsigned grid1 = (unsigned)(ntiles * batch);
+  int rc;
+  if constexpr (WARP) {                                          // the warp gathers single pixels: no vector form
+    rc = bf_launch_one<MODE, true, false>(who, a, grid1, smem, st);
+  } else {                                                       // quads of the map(s) the staging loads
+    const bool vec1 = (a.w % 4) == 0 && aligned16(a.prev) && (!BACK || aligned16(a.heat));
+    rc = vec1 ? bf_launch_one<MODE, false, true>(who, a, grid1, smem, st) : bf_launch_one<MODE, false, false>(who, a, grid1, smem, st);
+  }
+  if (rc) return rc;
   int slices, slice_len;
-  if (int rc = bf_slices("belief_smooth_step", batch, n, &slices, &slice_len)) return rc;
-  const bool vec2 = (n % 4) == 0 && aligned16(alpha) && aligned16(smooth) && aligned16(beta_out);
-  const dim3 grid2((unsigned)(slices * batch));
-  if (vec2)
-    hipLaunchKernelGGL(belief_smooth_finish_kernel<true>, grid2, dim3(256), 0, st, alpha, ori, cut, beta_out, smooth, scratch, rows,
-                       h, w, (int)ntiles, slices, slice_len);
-  else
-    hipLaunchKernelGGL(belief_smooth_finish_kernel<false>, grid2, dim3(256), 0, st, alpha, ori, cut, beta_out, smooth, scratch, rows,
-                       h, w, (int)ntiles, slices, slice_len);
-  return check_launch("belief_smooth_finish_kernel");
+  if ((rc = bf_slices(BACK ? "belief_smooth_step" : "belief_step", batch, n, &slices, &slice_len))) return rc;
+  const float* aux = BACK ? a.alpha : a.heat;
+  const bool vec2 = (n % 4) == 0 && aligned16(aux) && aligned16(a.out) && (!BACK || aligned16(a.beta_out));
+  hipLaunchKernelGGL((vec2 ? belief_finish_kernel<true, BACK> : belief_finish_kernel<false, BACK>), dim3((unsigned)(slices * batch)),
+                     dim3(256), 0, st, aux, ori, a.one_minus_a, a.floor_m, a.skip, a.out, a.beta_out, a.scratch, rows, a.h, a.w,
+                     (int)ntiles, slices, slice_len);
+  return check_launch("belief_finish_kernel");
 }
 
 }  // namespace ccvpe
@@ -836,53 +748,36 @@ static int bf_smooth_finish(const float* alpha, const float* ori, const int* cut
 extern "C" int ccvpe_belief_step_f32(const float* prior, const float* heat, const float* ori, const int* offsets,
                                      const float* taps, int radius, float outlier, const int* reset, float* post,
                                      double* scratch, double* rows, int batch, int h, int w, void* stream) {
+  const char* who = "belief_step";
   int ntx, nty;
-  if (int rc = bf_check("belief_step", prior, heat, ori, offsets, taps, radius, outlier, reset, post, scratch, rows, batch, h, w,
-                        &ntx, &nty))
+  if (int rc = bf_check(who, prior, heat, ori, offsets, taps, radius, outlier, reset, post, scratch, rows, batch, h, w, &ntx, &nty))
     return rc;
-  const long long ntiles = (long long)ntx * nty;
-  const size_t n = (size_t)h * w;
-  hipStream_t st = (hipStream_t)stream;
-  const float one_minus_a = 1.0f - outlier, floor_m = outlier / (float)n;
-  const int smem = (int)sizeof(float) * (BF_TH + 2 * radius) * (bf_pitch(radius) + BF_TW);      // 64 000 B at R = 32
-  const bool vec1 = (w % 4) == 0 && aligned16(prior);
-  const dim3 grid1((unsigned)(ntiles * batch));
-  if (vec1) {
-    auto kern = belief_predict_kernel<true>;
-    static DevCache lds_set;
-    if (int rc = ensure_dyn_lds(lds_set, kern, smem, "belief_step")) return rc;
-    hipLaunchKernelGGL(kern, grid1, dim3(256), smem, st, prior, heat, offsets, taps, radius, one_minus_a, floor_m, reset, post,
-                       scratch, h, w, ntx, nty);
-  } else {
-    auto kern = belief_predict_kernel<false>;
-    static DevCache lds_set;
-    if (int rc = ensure_dyn_lds(lds_set, kern, smem, "belief_step")) return rc;
-    hipLaunchKernelGGL(kern, grid1, dim3(256), smem, st, prior, heat, offsets, taps, radius, one_minus_a, floor_m, reset, post,
-                       scratch, h, w, ntx, nty);
-  }
-  if (int rc = check_launch("belief_predict_kernel")) return rc;
-  return bf_finish(heat, ori, one_minus_a, floor_m, reset, post, scratch, rows, batch, h, w, ntiles, st);
+  return bf_run<BF_SUM, false>(who, {prior, heat, nullptr, offsets, taps, reset, post, nullptr, scratch, radius, h, w, ntx, nty}, ori,
+                               outlier, rows, batch, stream);
 }
 
 extern "C" int ccvpe_belief_step_rigid_f32(const float* prior, const float* heat, const float* ori, const double* motion,
                                            const float* taps, int radius, float outlier, const int* reset, float* post,
                                            double* scratch, double* rows, int batch, int h, int w, void* stream) {
-  int ntx, nty;
+  const char* who = "belief_step_rigid";
+  int ntx, nty;                                                  // the shared checks report as belief_step
   if (int rc = bf_check("belief_step", prior, heat, ori, motion, taps, radius, outlier, reset, post, scratch, rows, batch, h, w,
                         &ntx, &nty))
     return rc;
-  if (reinterpret_cast<uintptr_t>(motion) & 7) return fail(CCVPE_EINVAL, "belief_step_rigid: motion must be 8-byte aligned");
-  const long long ntiles = (long long)ntx * nty;
-  hipStream_t st = (hipStream_t)stream;
-  const float one_minus_a = 1.0f - outlier, floor_m = outlier / (float)((size_t)h * w);
-  const int smem = (int)sizeof(float) * (BF_TH + 2 * radius) * (bf_pitch(radius) + BF_TW);
-  auto kern = belief_predict_rigid_kernel;
-  static DevCache lds_set;
-  if (int rc = ensure_dyn_lds(lds_set, kern, smem, "belief_step_rigid")) return rc;
-  hipLaunchKernelGGL(kern, dim3((unsigned)(ntiles * batch)), dim3(256), smem, st, prior, heat, motion, taps, radius, one_minus_a,
-                     floor_m, reset, post, scratch, h, w, ntx, nty);
-  if (int rc = check_launch("belief_predict_rigid_kernel")) return rc;
-  return bf_finish(heat, ori, one_minus_a, floor_m, reset, post, scratch, rows, batch, h, w, ntiles, st);
+  if (reinterpret_cast<uintptr_t>(motion) & 7) return fail(CCVPE_EINVAL, "%s: motion must be 8-byte aligned", who);
+  return bf_run<BF_SUM, true>(who, {prior, heat, nullptr, motion, taps, reset, post, nullptr, scratch, radius, h, w, ntx, nty}, ori,
+                              outlier, rows, batch, stream);
+}
+
+extern "C" int ccvpe_belief_viterbi_step_f32(const float* prior, const float* heat, const float* ori, const int* offsets,
+                                             const float* taps, int radius, float outlier, const int* reset, float* post,
+                                             double* scratch, double* rows, int batch, int h, int w, void* stream) {
+  const char* who = "belief_viterbi_step";
+  int ntx, nty;
+  if (int rc = bf_check(who, prior, heat, ori, offsets, taps, radius, outlier, reset, post, scratch, rows, batch, h, w, &ntx, &nty))
+    return rc;
+  return bf_run<BF_MAX, false>(who, {prior, heat, nullptr, offsets, taps, reset, post, nullptr, scratch, radius, h, w, ntx, nty}, ori,
+                               outlier, rows, batch, stream);
 }
 
 extern "C" int ccvpe_belief_smooth_step_f32(const float* beta, const float* heat, const float* alpha, const float* ori,
@@ -894,28 +789,8 @@ extern "C" int ccvpe_belief_smooth_step_f32(const float* beta, const float* heat
   if (int rc = bf_check(who, beta, heat, ori, offsets, taps, radius, outlier, cut, smooth, scratch, rows, batch, h, w, &ntx, &nty))
     return rc;
   if (int rc = bf_check_smooth(who, beta, heat, alpha, ori, beta_out, smooth, batch, h, w)) return rc;
-  const long long ntiles = (long long)ntx * nty;
-  const size_t n = (size_t)h * w;
-  hipStream_t st = (hipStream_t)stream;
-  const float one_minus_a = 1.0f - outlier, floor_m = outlier / (float)n;
-  const int smem = (int)sizeof(float) * (BF_TH + 2 * radius) * (bf_pitch(radius) + BF_TW);
-  const bool vec1 = (w % 4) == 0 && aligned16(heat) && aligned16(beta);
-  const dim3 grid1((unsigned)(ntiles * batch));
-  if (vec1) {
-    auto kern = belief_smooth_kernel<true>;
-    static DevCache lds_set;
-    if (int rc = ensure_dyn_lds(lds_set, kern, smem, who)) return rc;
-    hipLaunchKernelGGL(kern, grid1, dim3(256), smem, st, beta, heat, alpha, offsets, taps, radius, one_minus_a, floor_m, cut,
-                       beta_out, smooth, scratch, h, w, ntx, nty);
-  } else {
-    auto kern = belief_smooth_kernel<false>;
-    static DevCache lds_set;
-    if (int rc = ensure_dyn_lds(lds_set, kern, smem, who)) return rc;
-    hipLaunchKernelGGL(kern, grid1, dim3(256), smem, st, beta, heat, alpha, offsets, taps, radius, one_minus_a, floor_m, cut,
-                       beta_out, smooth, scratch, h, w, ntx, nty);
-  }
-  if (int rc = check_launch("belief_smooth_kernel")) return rc;
-  return bf_smooth_finish(alpha, ori, cut, beta_out, smooth, scratch, rows, batch, h, w, ntiles, st);
+  return bf_run<BF_BACK, false>(who, {beta, heat, alpha, offsets, taps, cut, smooth, beta_out, scratch, radius, h, w, ntx, nty}, ori,
+                                outlier, rows, batch, stream);
 }
 
 extern "C" int ccvpe_belief_smooth_step_rigid_f32(const float* beta, const float* heat, const float* alpha, const float* ori,
@@ -928,48 +803,8 @@ extern "C" int ccvpe_belief_smooth_step_rigid_f32(const float* beta, const float
     return rc;
   if (int rc = bf_check_smooth(who, beta, heat, alpha, ori, beta_out, smooth, batch, h, w)) return rc;
   if (reinterpret_cast<uintptr_t>(motion) & 7) return fail(CCVPE_EINVAL, "%s: motion must be 8-byte aligned", who);
-  const long long ntiles = (long long)ntx * nty;
-  hipStream_t st = (hipStream_t)stream;
-  const float one_minus_a = 1.0f - outlier, floor_m = outlier / (float)((size_t)h * w);
-  const int smem = (int)sizeof(float) * (BF_TH + 2 * radius) * (bf_pitch(radius) + BF_TW);
-  auto kern = belief_smooth_rigid_kernel;
-  static DevCache lds_set;
-  if (int rc = ensure_dyn_lds(lds_set, kern, smem, who)) return rc;
-  hipLaunchKernelGGL(kern, dim3((unsigned)(ntiles * batch)), dim3(256), smem, st, beta, heat, alpha, motion, taps, radius,
-                     one_minus_a, floor_m, cut, beta_out, smooth, scratch, h, w, ntx, nty);
-  if (int rc = check_launch("belief_smooth_rigid_kernel")) return rc;
-  return bf_smooth_finish(alpha, ori, cut, beta_out, smooth, scratch, rows, batch, h, w, ntiles, st);
-}
-
-extern "C" int ccvpe_belief_viterbi_step_f32(const float* prior, const float* heat, const float* ori, const int* offsets,
-                                             const float* taps, int radius, float outlier, const int* reset, float* post,
-                                             double* scratch, double* rows, int batch, int h, int w, void* stream) {
-  const char* who = "belief_viterbi_step";
-  int ntx, nty;
-  if (int rc = bf_check(who, prior, heat, ori, offsets, taps, radius, outlier, reset, post, scratch, rows, batch, h, w, &ntx, &nty))
-    return rc;
-  const long long ntiles = (long long)ntx * nty;
-  const size_t n = (size_t)h * w;
-  hipStream_t st = (hipStream_t)stream;
-  const float one_minus_a = 1.0f - outlier, floor_m = outlier / (float)n;
-  const int smem = (int)sizeof(float) * (BF_TH + 2 * radius) * (bf_pitch(radius) + BF_TW);
-  const bool vec1 = (w % 4) == 0 && aligned16(prior);
-  const dim3 grid1((unsigned)(ntiles * batch));
-  if (vec1) {
-    auto kern = belief_viterbi_kernel<true>;
-    static DevCache lds_set;
-    if (int rc = ensure_dyn_lds(lds_set, kern, smem, who)) return rc;
-    hipLaunchKernelGGL(kern, grid1, dim3(256), smem, st, prior, heat, offsets, taps, radius, one_minus_a, floor_m, reset, post,
-                       scratch, h, w, ntx, nty);
-  } else {
-    auto kern = belief_viterbi_kernel<false>;
-    static DevCache lds_set;
-    if (int rc = ensure_dyn_lds(lds_set, kern, smem, who)) return rc;
-    hipLaunchKernelGGL(kern, grid1, dim3(256), smem, st, prior, heat, offsets, taps, radius, one_minus_a, floor_m, reset, post,
-                       scratch, h, w, ntx, nty);
-  }
-  if (int rc = check_launch("belief_viterbi_kernel")) return rc;
-  return bf_finish(heat, ori, one_minus_a, floor_m, reset, post, scratch, rows, batch, h, w, ntiles, st);
+  return bf_run<BF_BACK, true>(who, {beta, heat, alpha, motion, taps, cut, smooth, beta_out, scratch, radius, h, w, ntx, nty}, ori,
+                               outlier, rows, batch, stream);
 }
 
 extern "C" int ccvpe_belief_backtrack_f32(const float* deltas, const float* ori, const int* offsets, const float* taps, int radius,

@@ -975,8 +975,8 @@ def belief_step(prior, heatmap, ori, offsets, taps, outlier=0.0, reset=None, pos
     (a non-zero entry starts that track from the measurement; its prior is not read).  post: a caller's [B,1,h,w] tensor that
     does not overlap prior; scratch: B * belief_partials(h, w) float64; out: a caller's [B,14] float64 slice of a larger table.
     Returns (rows [B,14] float64 — columns ccvpe_amd.tracking.PRED_Y ... SURVIVED, post)."""
-    return _belief_step("belief_step", "ccvpe_belief_step_f32", prior, heatmap, ori, offsets, "offsets", torch.int32, 2, taps,
-                        outlier, reset, post, scratch, out)
+    return _belief_step("belief_step", [(prior, "prior"), (heatmap, "heatmap")], ori, offsets, _OFFSETS, taps, outlier,
+                        (reset, "reset"), [(post, "post")], scratch, out)
 
 
 def belief_step_rigid(prior, heatmap, ori, motion, taps, outlier=0.0, reset=None, post=None, scratch=None, out=None):
@@ -985,8 +985,8 @@ def belief_step_rigid(prior, heatmap, ori, motion, taps, outlier=0.0, reset=None
     a12) of the INVERSE map, output pixel (y, x) reads the prior at ((a00 y + a01 x) + a02, (a10 y + a11 x) + a12), as
     tracking.rigid_motion and tracking.kitti_motions return them — then blurred by `taps` [B,2,2R+1] (centred:
     tracking.motion_taps(zeros, sigma, R)).  Every other argument, every check and the return value are belief_step's."""
-    return _belief_step("belief_step_rigid", "ccvpe_belief_step_rigid_f32", prior, heatmap, ori, motion, "motion", torch.float64, 6,
-                        taps, outlier, reset, post, scratch, out)
+    return _belief_step("belief_step_rigid", [(prior, "prior"), (heatmap, "heatmap")], ori, motion, _MOTION, taps, outlier,
+                        (reset, "reset"), [(post, "post")], scratch, out)
 
 
 def belief_viterbi_step(prior, heatmap, ori, offsets, taps, outlier=0.0, reset=None, post=None, scratch=None, out=None):
@@ -994,8 +994,8 @@ def belief_viterbi_step(prior, heatmap, ori, offsets, taps, outlier=0.0, reset=N
     predict become maxima, P[y,x] = max_i ky max_j kx prior[y - oy - i, x - ox - j]; the measure, the normalisation by the
     map's SUM, the reset rules and the 14 columns are belief_step's (SURVIVED = sum P).  The forward pass of the most likely
     path (tracking.MostLikelyPath).  Every argument, every check and the return value are belief_step's."""
-    return _belief_step("belief_viterbi_step", "ccvpe_belief_viterbi_step_f32", prior, heatmap, ori, offsets, "offsets", torch.int32,
-                        2, taps, outlier, reset, post, scratch, out)
+    return _belief_step("belief_viterbi_step", [(prior, "prior"), (heatmap, "heatmap")], ori, offsets, _OFFSETS, taps, outlier,
+                        (reset, "reset"), [(post, "post")], scratch, out)
 
 
 def belief_backtrack(deltas, ori, offsets, taps, rows, reset=None, out=None):
@@ -1036,42 +1036,54 @@ def belief_backtrack(deltas, ori, offsets, taps, rows, reset=None, out=None):
     return out
 
 
-def _belief_step(who, entry, prior, heatmap, ori, move, move_name, move_dtype, move_cols, taps, outlier, reset, post, scratch, out):
-    lib = _lib.load()
-    for t, nm in ((prior, "prior"), (heatmap, "heatmap"), (ori, "ori"), (taps, "taps"), (post, "post")):
+_OFFSETS, _MOTION = ("offsets", torch.int32, 2), ("motion", torch.float64, 6)       # a step's move: name, dtype, columns
+
+
+def _belief_step(who, ins, ori, move, move_spec, taps, outlier, skip, outs, scratch, out):
+    """The checks, the defaults and the call of the five step functions (entry point ccvpe_<who>_f32).  ins: the input maps as
+    (tensor, name), heatmap among them, in the entry point's order; outs: the output maps likewise, None = allocated here;
+    skip: (reset or cut, its name).  Returns (rows, the output maps last to first)."""
+    lib, entry = _lib.load(), "ccvpe_%s_f32" % who
+    others = dict((nm, t) for t, nm in ins)
+    heatmap = others.pop("heatmap")
+    for t, nm in ins + [(ori, "ori"), (taps, "taps")] + outs:
         _chk(t, nm)
+    move_name, move_dtype, move_cols = move_spec
     _chk(move, move_name, move_dtype)
-    _chk(reset, "reset", torch.int32)
+    _chk(skip[0], skip[1], torch.int32)
     for t, nm in ((scratch, "scratch"), (out, "out")):
         _chk(t, nm, torch.float64)
     if heatmap.dim() != 4 or heatmap.shape[1] != 1:
         raise ValueError("%s: heatmap [B,1,h,w] expected, got %s" % (who, tuple(heatmap.shape)))
     b, _, h, w = heatmap.shape
-    if prior.shape != heatmap.shape or ori.shape != (b, 2, h, w):
-        raise ValueError("%s: prior [B,1,h,w] like heatmap and ori [B,2,h,w] expected" % who)
+    if any(t.shape != heatmap.shape for t in others.values()) or ori.shape != (b, 2, h, w):
+        raise ValueError("%s: %s [B,1,h,w] like heatmap and ori [B,2,h,w] expected" % (who, " and ".join(others)))
     if taps.dim() != 3 or taps.shape[0] != b or taps.shape[1] != 2 or taps.shape[2] % 2 != 1:
         raise ValueError("%s: taps must be [%d,2,2R+1], got %s" % (who, b, tuple(taps.shape)))
     radius = (taps.shape[2] - 1) // 2
     if tuple(move.shape) != (b, move_cols):
         raise ValueError("%s: %s must be [%d,%d], got %s" % (who, move_name, b, move_cols, tuple(move.shape)))
-    if reset is not None and reset.numel() != b:
-        raise ValueError("%s: reset must hold one flag per track" % who)
+    if skip[0] is not None and skip[0].numel() != b:
+        raise ValueError("%s: %s must hold one flag per track" % (who, skip[1]))
     need = b * belief_partials(h, w)
     if scratch is None:
         scratch = _empty((need,), device=heatmap.device, dtype=torch.float64)
     elif scratch.numel() < need:
         raise ValueError("%s: scratch holds %d doubles, %d needed" % (who, scratch.numel(), need))
-    if post is None:
-        post = _empty(tuple(heatmap.shape), device=heatmap.device)
-    elif post.shape != heatmap.shape:
-        raise ValueError("%s: post must be %s, got %s" % (who, tuple(heatmap.shape), tuple(post.shape)))
+    maps = []
+    for t, nm in outs:
+        if t is None:
+            t = _empty(tuple(heatmap.shape), device=heatmap.device)
+        elif t.shape != heatmap.shape:
+            raise ValueError("%s: %s must be %s, got %s" % (who, nm, tuple(heatmap.shape), tuple(t.shape)))
+        maps.append(t)
     if out is None:
         out = _empty((b, 14), device=heatmap.device, dtype=torch.float64)
     elif tuple(out.shape) != (b, 14):
         raise ValueError("%s: out must be [%d,14], got %s" % (who, b, tuple(out.shape)))
-    check(getattr(lib, entry)(_ptr(prior), _ptr(heatmap), _ptr(ori), _ptr(move), _ptr(taps), radius, float(outlier),
-                              _ptr(reset), _ptr(post), _ptr(scratch), _ptr(out), b, h, w, _stream()), entry)
-    return out, post
+    args = [_ptr(t) for t, _ in ins] + [_ptr(ori), _ptr(move), _ptr(taps), radius, float(outlier), _ptr(skip[0])]
+    check(getattr(lib, entry)(*(args + [_ptr(t) for t in maps] + [_ptr(scratch), _ptr(out), b, h, w, _stream()])), entry)
+    return (out,) + tuple(reversed(maps))
 
 
 def belief_smooth_step(beta, heatmap, alpha, ori, offsets, taps, outlier=0.0, cut=None, beta_out=None, smooth=None, scratch=None,
@@ -1086,8 +1098,8 @@ def belief_smooth_step(beta, heatmap, alpha, ori, offsets, taps, outlier=0.0, cu
     input; scratch: B * belief_partials(h, w) float64; out: a caller's [B,14] float64 slice.
     Returns (rows [B,14] float64 — the columns of belief_step for the smoothed belief, RESET = the state, SURVIVED = sum B',
     smooth, beta_out)."""
-    return _belief_smooth_step("belief_smooth_step", "ccvpe_belief_smooth_step_f32", beta, heatmap, alpha, ori, offsets, "offsets",
-                               torch.int32, 2, taps, outlier, cut, beta_out, smooth, scratch, out)
+    return _belief_step("belief_smooth_step", [(beta, "beta"), (heatmap, "heatmap"), (alpha, "alpha")], ori, offsets, _OFFSETS, taps,
+                        outlier, (cut, "cut"), [(beta_out, "beta_out"), (smooth, "smooth")], scratch, out)
 
 
 def belief_smooth_step_rigid(beta, heatmap, alpha, ori, motion, taps, outlier=0.0, cut=None, beta_out=None, smooth=None,
@@ -1098,52 +1110,8 @@ def belief_smooth_step_rigid(beta, heatmap, alpha, ori, motion, taps, outlier=0.
     before the reversed-tap blur.  Not the exact adjoint of the rigid predict — a bilinear gather's adjoint is a scatter — but
     the same continuous model discretised the other way; equal to belief_smooth_step for angle 0 or quarter turns with
     whole-pixel shifts.  Every other argument, every check and the return value are belief_smooth_step's."""
-    return _belief_smooth_step("belief_smooth_step_rigid", "ccvpe_belief_smooth_step_rigid_f32", beta, heatmap, alpha, ori, motion,
-                               "motion", torch.float64, 6, taps, outlier, cut, beta_out, smooth, scratch, out)
-
-
-def _belief_smooth_step(who, entry, beta, heatmap, alpha, ori, move, move_name, move_dtype, move_cols, taps, outlier, cut, beta_out,
-                        smooth, scratch, out):
-    lib = _lib.load()
-    for t, nm in ((beta, "beta"), (heatmap, "heatmap"), (alpha, "alpha"), (ori, "ori"), (taps, "taps"), (beta_out, "beta_out"),
-                  (smooth, "smooth")):
-        _chk(t, nm)
-    _chk(move, move_name, move_dtype)
-    _chk(cut, "cut", torch.int32)
-    for t, nm in ((scratch, "scratch"), (out, "out")):
-        _chk(t, nm, torch.float64)
-    if heatmap.dim() != 4 or heatmap.shape[1] != 1:
-        raise ValueError("%s: heatmap [B,1,h,w] expected, got %s" % (who, tuple(heatmap.shape)))
-    b, _, h, w = heatmap.shape
-    if beta.shape != heatmap.shape or alpha.shape != heatmap.shape or ori.shape != (b, 2, h, w):
-        raise ValueError("%s: beta and alpha [B,1,h,w] like heatmap and ori [B,2,h,w] expected" % who)
-    if taps.dim() != 3 or taps.shape[0] != b or taps.shape[1] != 2 or taps.shape[2] % 2 != 1:
-        raise ValueError("%s: taps must be [%d,2,2R+1], got %s" % (who, b, tuple(taps.shape)))
-    radius = (taps.shape[2] - 1) // 2
-    if tuple(move.shape) != (b, move_cols):
-        raise ValueError("%s: %s must be [%d,%d], got %s" % (who, move_name, b, move_cols, tuple(move.shape)))
-    if cut is not None and cut.numel() != b:
-        raise ValueError("%s: cut must hold one flag per track" % who)
-    need = b * belief_partials(h, w)
-    if scratch is None:
-        scratch = _empty((need,), device=heatmap.device, dtype=torch.float64)
-    elif scratch.numel() < need:
-        raise ValueError("%s: scratch holds %d doubles, %d needed" % (who, scratch.numel(), need))
-    maps = []
-    for t, nm in ((beta_out, "beta_out"), (smooth, "smooth")):
-        if t is None:
-            t = _empty(tuple(heatmap.shape), device=heatmap.device)
-        elif t.shape != heatmap.shape:
-            raise ValueError("%s: %s must be %s, got %s" % (who, nm, tuple(heatmap.shape), tuple(t.shape)))
-        maps.append(t)
-    beta_out, smooth = maps
-    if out is None:
-        out = _empty((b, 14), device=heatmap.device, dtype=torch.float64)
-    elif tuple(out.shape) != (b, 14):
-        raise ValueError("%s: out must be [%d,14], got %s" % (who, b, tuple(out.shape)))
-    check(getattr(lib, entry)(_ptr(beta), _ptr(heatmap), _ptr(alpha), _ptr(ori), _ptr(move), _ptr(taps), radius, float(outlier),
-                              _ptr(cut), _ptr(beta_out), _ptr(smooth), _ptr(scratch), _ptr(out), b, h, w, _stream()), entry)
-    return out, smooth, beta_out
+    return _belief_step("belief_smooth_step_rigid", [(beta, "beta"), (heatmap, "heatmap"), (alpha, "alpha")], ori, motion, _MOTION,
+                        taps, outlier, (cut, "cut"), [(beta_out, "beta_out"), (smooth, "smooth")], scratch, out)
 
 
 def _loss_common(fn, name, tensors, extra):

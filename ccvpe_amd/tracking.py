@@ -39,6 +39,7 @@ tracks per `SequenceSmoother` and fixed-lag (online) smoothing; for the path the
 not a maximum, so its back-pointer needs a definition of its own — stored back-pointer maps, log-domain maps, bf16 maps and
 fixed-lag decoding.
 """
+import functools
 import math
 import os
 
@@ -469,15 +470,8 @@ class HistogramFilter(object):
 
     def __init__(self, n_tracks, hw=(512, 512), sigma_px=1.0, radius=None, outlier=0.0, device="cuda"):
         from . import ops
-        self.n_tracks, self.hw = int(n_tracks), (int(hw[0]), int(hw[1]))
-        self.sigma_px = float(sigma_px)
-        if self.sigma_px < 0:
-            raise ValueError("sigma_px must be >= 0")
-        self.radius = int(math.ceil(3 * self.sigma_px)) + 1 if radius is None else int(radius)
-        if not 0 <= self.radius <= MAX_RADIUS:
-            raise ValueError("radius %d outside [0, %d]: use a smaller sigma_px or pass radius" % (self.radius, MAX_RADIUS))
-        if not 0.0 <= float(outlier) <= 1.0:
-            raise ValueError("outlier must be in [0, 1]")
+        self.hw, self.sigma_px, self.radius, outlier = _drive_settings(hw, sigma_px, radius, outlier)
+        self.n_tracks = int(n_tracks)
         if self.n_tracks <= 0:
             raise ValueError("n_tracks must be positive")
         self.outlier, self.device = float(outlier), torch.device(device)
@@ -487,7 +481,6 @@ class HistogramFilter(object):
         self._scratch = torch.empty((self.n_tracks * ops.belief_partials(h, w),), device=self.device, dtype=torch.float64)
         self.rows = torch.zeros((self.n_tracks, 14), device=self.device, dtype=torch.float64)
         self._reset = torch.ones((self.n_tracks,), device=self.device, dtype=torch.int32)
-        self._zero_shift = None                                                 # step(motion=...): centred taps
 
     @property
     def belief(self):
@@ -510,35 +503,41 @@ class HistogramFilter(object):
         Both are tensors on any device or arrays.  Returns the rows [B,14] (columns PRED_Y ... SURVIVED): `rows_out` when given
         (a slice of a caller's table), else self.rows, which the next step overwrites."""
         from . import ops
-        if (shift_px is None) == (motion is None):
-            raise ValueError("step: pass exactly one of shift_px and motion")
         if tuple(heatmap.shape) != (self.n_tracks, 1) + self.hw:
             raise ValueError("step: heatmap must be %s, got %s" % ((self.n_tracks, 1) + self.hw, tuple(heatmap.shape)))
-        if motion is not None:
-            mot = motion if torch.is_tensor(motion) else torch.from_numpy(np.array(motion, dtype=np.float64))      # a copy
-            mot = mot.to(device=self.device, dtype=torch.float64)
-            if mot.numel() != 6 * self.n_tracks:
-                raise ValueError("step: motion must be [%d,6]" % self.n_tracks)
-            mot = mot.reshape(self.n_tracks, 6).contiguous()
-            if self._zero_shift is None:
-                self._zero_shift = torch.zeros((self.n_tracks, 2), device=self.device, dtype=torch.float64)
-            _, taps = motion_taps(self._zero_shift, self.sigma_px if sigma_px is None else sigma_px, self.radius)
-            rows = self.rows if rows_out is None else rows_out
-            ops.belief_step_rigid(self._buf[self._cur], heatmap, ori, mot, taps, outlier=self.outlier, reset=self._reset,
-                                  post=self._buf[1 - self._cur], scratch=self._scratch, out=rows)
-            self._reset.zero_()
-            self._cur = 1 - self._cur
-            return rows
-        shift = torch.as_tensor(shift_px).to(self.device)
-        if shift.numel() != 2 * self.n_tracks:
-            raise ValueError("step: shift_px must be [%d,2]" % self.n_tracks)
-        offsets, taps = motion_taps(shift, self.sigma_px if sigma_px is None else sigma_px, self.radius)
+        move, taps = _move_taps("step", shift_px, motion, (self.n_tracks,), self.device,
+                                self.sigma_px if sigma_px is None else sigma_px, self.radius)
         rows = self.rows if rows_out is None else rows_out
-        ops.belief_step(self._buf[self._cur], heatmap, ori, offsets, taps, outlier=self.outlier, reset=self._reset,
-                        post=self._buf[1 - self._cur], scratch=self._scratch, out=rows)
+        step = ops.belief_step if motion is None else ops.belief_step_rigid
+        step(self._buf[self._cur], heatmap, ori, move, taps, outlier=self.outlier, reset=self._reset,
+             post=self._buf[1 - self._cur], scratch=self._scratch, out=rows)
         self._reset.zero_()
         self._cur = 1 - self._cur
         return rows
+
+
+@functools.lru_cache(maxsize=8)
+def _zero_shift(count, device):
+    return torch.zeros((count, 2), device=device, dtype=torch.float64)
+
+
+def _move_taps(who, shift_px, motion, shape, device, sigma_px, radius):
+    """(move, taps) as the ops step functions take them, from exactly one of shift_px [*shape,2] and motion [*shape,6] (tensors
+    on any device or arrays; ValueError otherwise): the offsets int32 [n,2] and their taps, or the motion rows float64 [n,6] on
+    `device` with centred taps, n = prod(shape).  `who` names the caller in the messages."""
+    if (shift_px is None) == (motion is None):
+        raise ValueError("%s: pass exactly one of shift_px and motion" % who)
+    count = int(np.prod(shape))
+    if motion is None:
+        name, cols, move = "shift_px", 2, torch.as_tensor(shift_px).to(device)
+    else:
+        move = motion if torch.is_tensor(motion) else torch.from_numpy(np.array(motion, dtype=np.float64))      # a copy
+        name, cols, move = "motion", 6, move.to(device=device, dtype=torch.float64)
+    if move.numel() != cols * count:
+        raise ValueError("%s: %s must be [%s,%d]" % (who, name, ",".join(str(k) for k in shape), cols))
+    if motion is None:
+        return motion_taps(move.reshape(count, 2), sigma_px, radius)
+    return move.reshape(count, 6).contiguous(), motion_taps(_zero_shift(count, torch.device(device)), sigma_px, radius)[1]
 
 
 def _drive_settings(hw, sigma_px, radius, outlier):
@@ -578,26 +577,13 @@ class SequenceSmoother(object):
         Returns {"filtered": rows [T,14] of the forward pass, "smoothed": rows [T,14] of the smoothed beliefs (RESET: 0 chained,
         1 last frame of its segment, 2 the message died out; SURVIVED: the back-predicted mass), "beliefs": the smoothed
         beliefs [T,1,h,w] with keep_beliefs, else None}, all on the device."""
-        if (shift_px is None) == (motion is None):
-            raise ValueError("run: pass exactly one of shift_px and motion")
         if heat.dim() != 4 or tuple(heat.shape[1:]) != (1,) + self.hw or heat.shape[0] < 1:
             raise ValueError("run: heat must be [T,1,%d,%d], got %s" % (self.hw + (tuple(heat.shape),)))
         n = int(heat.shape[0])
         if tuple(ori.shape) != (n, 2) + self.hw:
             raise ValueError("run: ori must be [%d,2,%d,%d], got %s" % ((n,) + self.hw + (tuple(ori.shape),)))
         dev = self.device
-        if motion is not None:
-            move = motion if torch.is_tensor(motion) else torch.from_numpy(np.array(motion, dtype=np.float64))
-            move = move.to(device=dev, dtype=torch.float64)
-            if move.numel() != 6 * n:
-                raise ValueError("run: motion must be [%d,6]" % n)
-            move = move.reshape(n, 6).contiguous()
-            _, taps = motion_taps(torch.zeros((n, 2), device=dev, dtype=torch.float64), self.sigma_px, self.radius)
-        else:
-            shift = torch.as_tensor(shift_px).to(dev)
-            if shift.numel() != 2 * n:
-                raise ValueError("run: shift_px must be [%d,2]" % n)
-            move, taps = motion_taps(shift, self.sigma_px, self.radius)
+        move, taps = _move_taps("run", shift_px, motion, (n,), dev, self.sigma_px, self.radius)
         reset = torch.zeros((n,), device=dev, dtype=torch.int32)
         if starts is not None:
             st = torch.as_tensor(np.asarray(starts).reshape(-1).astype(np.int32))
@@ -681,10 +667,7 @@ class MostLikelyPath(object):
         if tuple(ori.shape) != (n, b, 2, h, w):
             raise ValueError("run: ori must be [%d,%d,2,%d,%d], got %s" % (n, b, h, w, tuple(ori.shape)))
         dev = self.device
-        shift = torch.as_tensor(shift_px).to(dev)
-        if shift.numel() != 2 * n * b:
-            raise ValueError("run: shift_px must be [%d,%d,2]" % (n, b))
-        offsets, taps = motion_taps(shift.reshape(n * b, 2), self.sigma_px, self.radius)
+        offsets, taps = _move_taps("run", shift_px, None, (n, b), dev, self.sigma_px, self.radius)
         offsets, taps = offsets.reshape(n, b, 2), taps.reshape(n, b, 2, 2 * self.radius + 1)
         reset = torch.zeros((n, b), device=dev, dtype=torch.int32)
         if starts is not None:

@@ -17,44 +17,21 @@ device, 512 x 512, R = 8, at B = 1 and B = 64: three alternating rounds, device 
 
 Writes track_step_timing.json into --out."""
 import argparse
-import json
-import os
-import sys
 
 import numpy as np
 import torch
 import torch.nn.functional as F
 
-ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..")
-sys.path.insert(0, ROOT)
-from ccvpe_amd import ops, tracking  # noqa: E402
+from track_common import ALPHA, H, R, W, floor, scene, timed, write
+from ccvpe_amd import ops, tracking  # noqa: E402  (track_common puts the repository root on sys.path)
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--out", default=".")
 args = ap.parse_args()
-H = W = 512
-R, ALPHA = 8, 0.02
-
-
-def timed(fn, n, warm):
-    for _ in range(warm):
-        fn()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(n):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) * 1000.0 / n          # microseconds per step
 
 
 def case(B, n):
-    g = torch.Generator(device="cuda").manual_seed(B)
-    prior = torch.softmax(torch.randn((B, H * W), device="cuda", generator=g) * 4, 1).reshape(B, 1, H, W)
-    heat = torch.softmax(torch.randn((B, H * W), device="cuda", generator=g) * 4, 1).reshape(B, 1, H, W)
-    ori = F.normalize(torch.randn((B, 2, H, W), device="cuda", generator=g), dim=1)
-    shift = (torch.rand((B, 2), device="cuda", generator=g, dtype=torch.float64) - 0.5) * 12
+    prior, heat, _, ori, shift, _ = scene(B)
     offsets, taps = tracking.motion_taps(shift, 2.5, R)
     post = torch.empty_like(prior)
     scratch = torch.empty((B * ops.belief_partials(H, W),), device="cuda", dtype=torch.float64)
@@ -113,10 +90,7 @@ def case(B, n):
         res["copy_us"].append(timed(lambda: dst.copy_(src), n, 20))
     for k in ("hip", "filter", "hip_rb", "torch", "torch_shared", "copy"):
         res[k + "_median_us"] = float(np.median(res[k + "_us"]))
-    nbytes = B * H * W * 4
-    res["copy_GBps"] = 2 * nbytes / res["copy_median_us"] / 1e3              # read + write
-    res["step_bytes"] = 5 * nbytes
-    res["floor_us"] = res["step_bytes"] / res["copy_GBps"] / 1e3
+    floor(res, B, 5)
     res["hip_over_floor"] = res["hip_median_us"] / res["floor_us"]
     res["torch_over_hip"] = res["torch_median_us"] / res["hip_median_us"]
     res["torch_over_hip_rb"] = res["torch_median_us"] / res["hip_rb_median_us"]
@@ -125,7 +99,4 @@ def case(B, n):
 
 
 out = {"shape": [H, W], "radius": R, "cases": [case(1, 2000), case(64, 200)]}
-os.makedirs(args.out, exist_ok=True)
-with open(os.path.join(args.out, "track_step_timing.json"), "w") as f:
-    json.dump(out, f, indent=1)
-print(json.dumps(out))
+write(out, args.out, "track_step_timing.json")
