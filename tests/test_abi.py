@@ -389,3 +389,39 @@ def test_forward_kernel_table_matches_the_band_plan_query():
     assert lib.ccvpe_mbconv_front_route(h, w, cin, 6 * cin, k, s, 1, 3) == 2, "route says band for a shape the launcher refuses"
     assert lib.ccvpe_mbconv_band_plan(h, w, cin, 6 * cin, k, s, 3) == 0
     assert lib.ccvpe_mbconv_band_plan(16, 16, 192, 1152, 5, 1, 0) == 0               # no batch
+
+
+def test_wgrad_kernel_table_matches_the_planner_queries():
+    """Host-only: every row of tests/wgrad_kernel_shapes.py (the shapes tests/test_wgrad_forms_gpu.py checks against float64) still
+    gets the tile and the split count it is there for, the restated planner agrees with the row, and the rows reach every
+    conv_wgrad_kernel instantiation of the traced training step."""
+    import wgrad_kernel_shapes as S
+    lib = _lib.load()
+    rows = S.rows()
+    assert [r.num for r in rows] == list(range(1, 24))
+    for r in rows:
+        ho, wo, m, ctot, taps, ncols = S.dims(r)
+        assert S.plan(r) == r.plan, (r.name, S.plan(r))
+        tile = lib.ccvpe_conv_wgrad_tile(r.n, ncols)
+        assert (tile >> 16, tile & 0xffff) == (r.plan.tile, S.tile_cols(r.plan.tile)), (r.name, tile >> 16, tile & 0xffff)
+        floats = lib.ccvpe_conv_wgrad_scratch_floats(r.b, r.h, r.w, r.k, r.k, r.stride, r.pad, ctot, r.n)
+        assert floats == r.plan.s * (r.n * ncols + r.n), (r.name, floats // (r.n * ncols + r.n))
+        assert r.ldy % 4 == 0 and r.ldy >= r.n and r.ld0 >= r.c0 and r.c0 % 4 == 0 and r.c1 % 4 == 0, r.name
+        assert 4 * max(r.b * r.h * r.w * (r.ld0 + r.c1), m * r.ldy, floats) < 32 << 20, "%s: a tensor above 32 MB" % r.name
+        if r.kind == "gated":
+            assert r.k == 1 and r.c1 == 0 and r.plan.tile != 128, r.name
+    reached = {S.form(r) for r in rows}
+    assert len(S.TRACED) == 11 and set(S.TRACED) <= reached, sorted(set(S.TRACED) - reached)
+    # the launcher edges the table is there for
+    plans = [r.plan for r in rows]
+    assert all(p.pps % S.WG_BP == 0 for p in plans) and any(p.last_px % S.WG_BP for p in plans)       # a split that ends mid-stage
+    assert any(p.empty for p in plans) and any(p.s == 1024 for p in plans)
+    assert any(p.s == 4096 // (p.tiles_n * p.tiles_c) and p.empty for p in plans)                      # S limited by the tile count
+    assert {p.ln_dw for p in plans} == {1, 4, 16, 64} and {p.ln_bias for p in plans} == {1, 4, 16, 64}
+    assert {p.grid_mod8 for p in plans} >= {0, 2, 6, 7}
+    assert any(r.ldy > r.n for r in rows) and any(r.ld0 > r.c0 for r in rows) and any(r.n % 4 for r in rows)
+    assert any(r.stride == 2 for r in rows) and any(r.kind == "deconv" for r in rows)
+    assert any(S.dims(r)[1] < S.WG_BP // 4 for r in rows)                                             # Wo < 8: several carries per stage
+    for p in plans:
+        # the model's merge term: at most S roundings (a chain's first addition is to zero and exact)
+        assert S.merge_chain(p.s, p.ln_dw) - 1 <= p.s and S.merge_chain(p.s, p.ln_bias) - 1 <= p.s, p
